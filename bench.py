@@ -11,6 +11,12 @@ main.py:88-92), mean/sigma are the DynamicsModel prior (dynamics.py:381-384).
 Multi-GPU: one process per GPU (torchrun), each GPU owns `--batch` envs
 (weak scaling, no collective on the data path; RCCL only for the barrier and
 the max-over-ranks time).  Rank 0 prints one JSON line.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps, writes the last step's outputs if --dump-outputs DIR is
+given, and prints the line.  Everything measured beside the headline figure
+(the profiled re-run of the plan for the roofline's per-step GPU time, the
+in-kernel span, the CPU baselines, config 1's parity episode) runs with --full.
 """
 import argparse
 import json
@@ -108,7 +114,18 @@ def parse():
                     help="config 5's backward: jac = the forward keeps d final / d u (rcbf_obs_safe_action_jac) and "
                          "the backward applies it (rcbf_safe_action_apply_jac), as the autograd op runs it; resolve "
                          "= the plain forward and the re-solving backward (rcbf_obs_safe_action_backward)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the profiled re-run "
+                         "of the AQL plan (roofline kernel_ms / achieved / frac), the in-kernel span, the CPU "
+                         "baselines in a child process, config 1's parity episode.  Without it a run sets up, warms "
+                         "up, times the steps and prints the line.  --extra and --record imply it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (obs, u, reward, cost, done, "
+                         "state, ...) as DIR/<name>.npy, float32 or float64, at most 64 MB in all (beyond that a "
+                         "fixed seeded sample of the envs, their indices in sample_rows.npy)")
     args = ap.parse_args()
+    if args.extra or args.record:
+        args.full = True
     preset = {1: dict(env="SimulatedCars", batch=1, workload="closed_loop"),
               2: dict(env="SimulatedCars", batch=4096, workload="step", prior="rows", prior_values="maxstd"),
               3: dict(env="Unicycle", hazards=3, batch=4096, workload="step"),
@@ -172,6 +189,35 @@ def largest_divisor_le(n, cap):
         if n % s == 0:
             return s
     return 1
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> tensor or ndarray, first axis the
+    env / row; None entries skipped) as path/<name>.npy (<name>_rank<r>.npy
+    when there are several ranks).  float64 stays, everything else is written
+    as float32.  If they exceed DUMP_MAX_BYTES together, the same rows of
+    every array are kept: a sorted sample drawn with a fixed seed, its indices
+    in sample_rows.npy."""
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        rows = min(a.shape[0] for a in host.values())
+        per_row = sum(a.nbytes // a.shape[0] for a in host.values()) + 8
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_MAX_BYTES // per_row, replace=False))
+        host = {name: np.ascontiguousarray(a[keep]) for name, a in host.items()}
+        host["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, a in host.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
 
 
 def cpu_baseline(env_name, hazards, seconds, B=65536):
@@ -688,13 +734,15 @@ def main():
         # untimed rehearsal of the timed sequence (sync, event, replays, event, sync): the first
         # such sequence after set-up spends ~35-50 us instead of ~15 us of host time in the replay
         # call (profiles/r02/bench_rehearsal_r02y.txt); part of the warm-up, not of the K timed steps
+        # (at most 4 replays of the plan, so that with many replays per run it does not grow with --steps)
+        rehearsed = min(reps, 4)
         sync()
         ev0.record()
-        for _ in range(reps):
+        for _ in range(rehearsed):
             graph.replay()
         ev1.record()
         sync()
-        untimed += reps * S
+        untimed += rehearsed * S
     shard.barrier(world)
     sync()
     # HIP events bracket the HIP launches; the AQL dispatches run on no HIP stream (their per-launch time
@@ -717,8 +765,13 @@ def main():
     # per fused-step launch, HIP events on the launch stream (torch's current stream)
     kern_ms = ev0.elapsed_time(ev1) / args.steps if events else 0.0
     env.check_failures()
+    if args.dump_outputs:
+        if args.cpu_dry_run:
+            raise SystemExit("--dump-outputs: a dry run computes nothing")
+        # now, before any untimed re-run below writes the same buffers again
+        dump_outputs(args.dump_outputs, dict(ctx["outs"], **ctx["results"]()), rank, world)
     aql_times = {}
-    if args.launch == "aql" and not args.cpu_dry_run:
+    if args.launch == "aql" and args.full and not args.cpu_dry_run:
         # no HIP stream carries the AQL dispatches: the per-launch duration comes from the packet processor's
         # dispatch timestamps of the same S steps, re-run profiled right after the timed region
         aql_times = aql_dispatch_times(env, layer, ctx, graph, S)
@@ -730,6 +783,8 @@ def main():
     value = shard.whole_job_rate(world, B, args.steps, el)
     bps = bytes_per_step(args)
     achieved = B * bps / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    # the AQL plan's per-step GPU time takes the profiled re-run: without --full it is not measured
+    unmeasured = args.launch == "aql" and not args.full and not args.cpu_dry_run
     short = workload_short(args)
     traffic, traffic_src = pmc_traffic_file(short, B)
     kernels = dominant_kernels(args, B)
@@ -737,7 +792,7 @@ def main():
     k_us_rp, rp_src = rocprof_kernel_us(short, B, kernels, rp_form, args.launch)
     k_us_rec, rec_src = roofline_record(short, B, rp_form, args.launch)
     span = {}
-    if world == 1 and not args.cpu_dry_run and not args.no_span and args.workload == "step":
+    if world == 1 and args.full and not args.cpu_dry_run and not args.no_span and args.workload == "step":
         span = measure_span(env, layer, ctx, dev, B, bps, queue=getattr(graph, "queue", None))
     extra = {}
     if args.extra and rank == 0 and not args.cpu_dry_run and args.workload == "step":
@@ -767,6 +822,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "untimed_steps_executed": untimed,
+        "full": bool(args.full),
         "ms_per_step": round(el / args.steps * 1e3, 5),
         "higher_is_better": True,
         "scaling": args.scaling,
@@ -787,11 +843,12 @@ def main():
                                    if dist.is_available() and dist.is_initialized() else None),
                    "prior": args.prior, "qp_active_frac_at_start": round(active_frac, 4),
                    "host_cores_per_rank": len(host_cores) if host_cores else None},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+        "roofline": {"bound": "hbm", "achieved": None if unmeasured else round(achieved, 1), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s",
+                     "frac": None if unmeasured else round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      "traffic_source": traffic_src,
                      "kernel": " + ".join(kernels), "bytes_per_env_step": bps, "bytes_per_launch": B * bps,
-                     "kernel_ms": round(kern_ms, 5), "host_submit_ms": round(t_sub * 1e3, 4),
+                     "kernel_ms": None if unmeasured else round(kern_ms, 5), "host_submit_ms": round(t_sub * 1e3, 4),
                      "kernel_us_rocprof": k_us_rp,
                      "frac_rocprof": round(B * bps / (k_us_rp * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if k_us_rp else None,
                      "rocprof_source": rp_src,
@@ -828,6 +885,12 @@ def main():
                                      "(aql_dispatch_times.period_us; the AQL counterpart of HIP events around the "
                                      "region); host_submit_ms = host time of the timed run call (submission AND the "
                                      "wait for completion)")
+    if unmeasured:
+        rec["roofline"]["timing"] = ("frac_wall = bytes_per_launch / ms_per_step, the timed region's wall clock; "
+                                     "kernel_ms, achieved and frac (the per-step GPU time from the packet "
+                                     "processor's timestamps of a profiled re-run of the plan) and the in-kernel "
+                                     "span are measured with --full; host_submit_ms = host time of the timed run "
+                                     "call (submission AND the wait for completion)")
     if args.rehearse_shared_gpu:
         rec["rehearsal"] = (f"{world} ranks sharing GPU 0 over a gloo group: a check of the N > 1 launch path, "
                             "NOT a scaling measurement (the ranks contend for one GPU)")
@@ -839,7 +902,7 @@ def main():
                               "max": round(ms[-1], 5)}
     if extra:
         rec["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.cpu_dry_run:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.cpu_dry_run:
         if host_mask:  # the child starts with every allowed core
             os.sched_setaffinity(0, host_mask)
         rec.update(cpu_baselines_in_child(args))
@@ -881,7 +944,7 @@ def bench_closed_loop(args):
     CascadeCBFLayer(env, gamma_b=20, k_d=3).get_u_safe (cbf_qp.py:29-53) on rcbf_cascade_u_safe_sync, then
     env.step(u_nom + u_safe) on rcbf_env_step_sync -- every call the reference's own surface, per step.
     Timed: exactly --steps closed-loop steps (episodes of 300 from the golden reset, resetting when done),
-    after --warmup untimed ones.  Then, untimed, one full episode is checked against the reference's own
+    after --warmup untimed ones.  Then, with --full, untimed, one full episode is checked against the reference's own
     closed loop (tests/golden/closed_loop_cars.npz) and the C oracle's loop is timed on one core beside it.
     One process (the loop is single-env, host-driven: replicas only across GPUs)."""
     import types
@@ -923,6 +986,21 @@ def bench_closed_loop(args):
     obs = run(args.steps, obs)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:  # what the last timed step returned and left behind
+        dump_outputs(args.dump_outputs, {"obs": np.asarray(obs, np.float64), "state": env.state})
+    line = {"metric": METRICS.get(1, METRICS[0]), "value": round(args.steps / el, 1), "unit": "safe env steps/s",
+            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
+            "ms_per_step": round(el / args.steps * 1e3, 5),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64 rows / f64 QP / f64 env",
+            "data": "the reference's config-1 episode: golden reset draw, the hand controller's actions",
+            "config": {"workload": "SimulatedCars Cascade closed loop (config 1, envs/simulated_cars_env.py:161-228): "
+                                   "1 env, hand controller + DynamicsModel prior + CascadeCBFLayer.get_u_safe "
+                                   "(rcbf_cascade_u_safe_sync) + env.step (rcbf_env_step_sync), host-driven per step",
+                       "baseline_config": 1, "batch_per_gpu": 1, "global_batch": 1, "env": "SimulatedCars",
+                       "parallelism": "single env (replicas only)"}}
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
     # parity, untimed: one whole episode against the reference's own loop
     rec = []
     run(300, reset(), rec)
@@ -935,16 +1013,7 @@ def bench_closed_loop(args):
               "state": rel(xs, gold["state"][1:]), "steps": 300,
               "against": "tests/golden/closed_loop_cars.npz (the reference's own closed loop, exact QP)"}
     ok = parity["u_safe"] <= 1e-6 and parity["state"] <= 1e-8
-    line = {"metric": METRICS.get(1, METRICS[0]), "value": round(args.steps / el, 1), "unit": "safe env steps/s",
-            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 5),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64 rows / f64 QP / f64 env",
-            "data": "the reference's config-1 episode: golden reset draw, the hand controller's actions",
-            "config": {"workload": "SimulatedCars Cascade closed loop (config 1, envs/simulated_cars_env.py:161-228): "
-                                   "1 env, hand controller + DynamicsModel prior + CascadeCBFLayer.get_u_safe "
-                                   "(rcbf_cascade_u_safe_sync) + env.step (rcbf_env_step_sync), host-driven per step",
-                       "baseline_config": 1, "batch_per_gpu": 1, "global_batch": 1, "env": "SimulatedCars",
-                       "parallelism": "single env (replicas only)"},
-            "parity": dict(parity, ok=ok)}
+    line["parity"] = dict(parity, ok=ok)
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_closed_loop(noise, args.cpu_seconds)
     print(json.dumps(line), flush=True)
@@ -1076,7 +1145,9 @@ def setup_gpu(args, dev, rank, B):
         untimed += 2 + 2 * S
     torch.cuda.synchronize()
     env.check_failures()
-    ctx = {"pool": pool, "mean": mean, "sigma": sigma, "layout": layout, "outs": outs}
+    ctx = {"pool": pool, "mean": mean, "sigma": sigma, "layout": layout, "outs": outs,
+           # what a step returns beside `outs` (safe_step: obs) and leaves behind (the env states)
+           "results": lambda: {"obs": env.obs, "state": env.state, "aux": env.aux}}
     return env, layer, graph, S, active_frac, untimed, ctx
 
 
@@ -1157,7 +1228,8 @@ def setup_sac_update(args, dev, rank, B):
                 raise Exception("QP Failed to solve")
     _Fails().check_failures()
     untimed = 1 + max(args.warmup, 1) + 2 + 2 * S
-    return _Fails(), layer, graph, S, active_frac, untimed, {}
+    ctx = {"outs": {"u": uo, "grad_u_rl": gu}, "results": lambda: {"jac": jac} if args.sac_bwd == "jac" else {}}
+    return _Fails(), layer, graph, S, active_frac, untimed, ctx
 
 
 def sac_update_safe_action(env, layer, dev):

@@ -11,7 +11,7 @@ for r in 1 2 3; do for w in "$@"; do
     c3) a="--config 3";; c4) a="--config 4";; c4s) a="--batch 32768";; c5) a="--config 5";; esac
   for n in prod $NAMES; do
     if [ "$n" = prod ]; then lib=""; else lib="RCBF_HIP_LIB=build/variants/librcbf_$n.so"; fi
-    env $lib timeout -k 10 100 python bench.py --no-cpu-baseline --no-span $a > $O/${n}_$w.log 2>&1 || exit 1
+    env $lib timeout -k 10 100 python bench.py --full --no-cpu-baseline --no-span $a > $O/${n}_$w.log 2>&1 || exit 1
     echo "$n $w $(grep -o '"ms_per_step": [0-9.]*\|"kernel_ms": [0-9.]*' $O/${n}_$w.log | tr '\n' ' ')" >> $O/sum.txt
   done
 done; done

@@ -61,65 +61,65 @@ for step in "$@"; do
   case $step in
     smoke)  run smoke 400 python __graft_entry__.py smoke ;;
     pytest) run pytest 900 python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeout-method thread ;;
-    bench)  run bench 600 python bench.py ;;
-    driver) run driver 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ;;
-    drvgraph) run drvgraph 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --launch graph ;;
+    bench)  run bench 600 python bench.py --full ;;
+    driver) run driver 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ;;
+    drvgraph) run drvgraph 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --launch graph ;;
     recdrv)  # the driver's command with its roofline record (per-step GPU time, dispatch timestamps, span stamps, clock)
-      run recdrv 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
+      run recdrv 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
         --record "$OUT/roofline_record_driver_form_aql_cars_B65536_$TAG.json" ;;
-    recdef) run recdef 300 python bench.py --no-cpu-baseline --record "$OUT/roofline_record_aql_cars_B65536_$TAG.json" ;;
+    recdef) run recdef 300 python bench.py --full --no-cpu-baseline --record "$OUT/roofline_record_aql_cars_B65536_$TAG.json" ;;
     pmcbusy)  # GRBM_GUI_ACTIVE / SQ_BUSY_CYCLES pass of the driver's command -> busy us per dispatch (needs recdrv first)
       run pmcbusy 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d "$OUT/pmcbusy" -o run -- \
-        python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-span
+        python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-span
       [ -f "$OUT/pmcbusy/run_counter_collection.csv" ] && python scripts/pmc_busy.py "$OUT/pmcbusy/run_counter_collection.csv" \
         "$(wl_kernel cars)" "$OUT/roofline_record_driver_form_aql_cars_B65536_$TAG.json" \
         "$OUT/pmc_busy_driver_form_aql_cars_B65536_$TAG.json" > /dev/null ;;
-    benchx) run benchx 600 python bench.py --extra --no-cpu-baseline ;;
+    benchx) run benchx 600 python bench.py --full --extra --no-cpu-baseline ;;
     aqltest) run aqltest 300 python -u -m pytest tests/test_gpu_aql.py -q -rf --timeout 200 --timeout-method thread ;;
     aqltl) run aqltl 300 python -u scripts/exp_aql_timeline.py ;;
     scal)  # per-shard batches for the 1 -> 8 projection (scripts/scaling_projection.py), both command forms
       for b in 65536 32768 16384 8192; do
-        run "scal_d_$b" 200 python bench.py --no-cpu-baseline --no-span --batch "$b" --steps 20 --warmup 5
-        run "scal_l_$b" 200 python bench.py --no-cpu-baseline --no-span --batch "$b"
+        run "scal_d_$b" 200 python bench.py --full --no-cpu-baseline --no-span --batch "$b" --steps 20 --warmup 5
+        run "scal_l_$b" 200 python bench.py --full --no-cpu-baseline --no-span --batch "$b"
       done
       python scripts/scaling_projection.py "$OUT/scaling_projection_$TAG.json" "$OUT"/scal_*.log > /dev/null ;;
-    drvaql) run drvaql 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --launch aql ;;
-    benchaql) run benchaql 300 python bench.py --no-cpu-baseline --launch aql ;;
+    drvaql) run drvaql 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --launch aql ;;
+    benchaql) run benchaql 300 python bench.py --full --no-cpu-baseline --launch aql ;;
     sweep)  # waves per SIMD: B = 32768 (half the SIMDs), 65536 (one wave each), 98304, 131072 (two)
       for w in cars uni3 uni5; do for b in 32768 65536 98304 131072; do
-        run "sweep_${w}_$b" 300 python bench.py --no-cpu-baseline --batch "$b" $(wl_args "$w")
+        run "sweep_${w}_$b" 300 python bench.py --full --no-cpu-baseline --batch "$b" $(wl_args "$w")
       done; done ;;
-    b_*)    run "b_$wl" 300 python bench.py --no-cpu-baseline $(wl_args "$wl") ;;
-    bc_*)   run "bc_$wl" 400 python bench.py $(wl_args "$wl") ;;  # with the CPU baselines
+    b_*)    run "b_$wl" 300 python bench.py --full --no-cpu-baseline $(wl_args "$wl") ;;
+    bc_*)   run "bc_$wl" 400 python bench.py --full $(wl_args "$wl") ;;  # with the CPU baselines
     prof_*)
       run "prof_$wl" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$wl" -o run -- \
-        python3 bench.py --no-cpu-baseline $(wl_args "$wl")
+        python3 bench.py --full --no-cpu-baseline $(wl_args "$wl")
       [ -f "$OUT/prof_$wl/run_kernel_trace.csv" ] && python scripts/trace_summary.py "$OUT/prof_$wl/run_kernel_trace.csv" \
         "$(wl_kernel "$wl")" "$OUT/$(wl_name "$wl")_kernel_trace_summary.json"
       [ -f "$OUT/prof_$wl/run_kernel_stats.csv" ] && cp "$OUT/prof_$wl/run_kernel_stats.csv" "$OUT/kernel_stats_$(wl_name "$wl")_$TAG.csv" ;;
     profdrv)  # the driver's own command under the tracer (the AQL launch: rocprofv3 intercepts the library's queue)
       run profdrv 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profdrv" -o run -- \
-        python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
+        python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
       [ -f "$OUT/profdrv/run_kernel_trace.csv" ] && python scripts/trace_summary.py "$OUT/profdrv/run_kernel_trace.csv" \
         "$(wl_kernel cars)" "$OUT/cars_B65536_driver_form_aql_kernel_trace_summary.json"
       [ -f "$OUT/profdrv/run_kernel_stats.csv" ] && cp "$OUT/profdrv/run_kernel_stats.csv" "$OUT/kernel_stats_driver_form_aql_cars_B65536_$TAG.csv" ;;
     pmc_*)
       run "pmcf_$wl" 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmcf_$wl" -o run -- \
-        python3 bench.py --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
+        python3 bench.py --full --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
       run "pmcw_$wl" 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmcw_$wl" -o run -- \
-        python3 bench.py --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
+        python3 bench.py --full --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
       if [ -f "$OUT/pmcf_$wl/run_counter_collection.csv" ] && [ -f "$OUT/pmcw_$wl/run_counter_collection.csv" ]; then
         python scripts/pmc_traffic.py "$OUT/pmcf_$wl/run_counter_collection.csv" "$OUT/pmcw_$wl/run_counter_collection.csv" \
           "$(wl_kernel "$wl")" "$OUT/pmc_traffic_$(wl_name "$wl").json" workload="$(wl_name "$wl")" > /dev/null
       fi ;;
     sq_*)
       run "sq_$wl" 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES \
-        --output-format csv -d "$OUT/sq_$wl" -o run -- python3 bench.py --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
+        --output-format csv -d "$OUT/sq_$wl" -o run -- python3 bench.py --full --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
       [ -f "$OUT/sq_$wl/run_counter_collection.csv" ] && python scripts/pmc_sq.py "$OUT/sq_$wl/run_counter_collection.csv" \
         "$(wl_kernel "$wl")" > "$OUT/pmc_sq_$(wl_name "$wl").txt" ;;
     if_*)  # instruction-fetch waits: SQ wave-cycle shares and instruction-cache misses, one pass
       run "if_$wl" 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_IFETCH SQ_INSTS_VALU SQC_ICACHE_MISSES \
-        --output-format csv -d "$OUT/if_$wl" -o run -- python3 bench.py --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
+        --output-format csv -d "$OUT/if_$wl" -o run -- python3 bench.py --full --no-cpu-baseline --no-graph --steps 50 --warmup 5 $(wl_args "$wl")
       [ -f "$OUT/if_$wl/run_counter_collection.csv" ] && python scripts/pmc_sq.py "$OUT/if_$wl/run_counter_collection.csv" \
         "$(wl_kernel "$wl")" > "$OUT/pmc_ifetch_$(wl_name "$wl").txt" ;;
     pair)  # the unicycle lane-pair study build vs the product (scripts/uni_pair_study.py)
@@ -176,7 +176,7 @@ for step in "$@"; do
       fi ;;
     soak)   run soak 600 python -u -m pytest tests/test_gpu_headline_parity.py -q -rf -k soak --timeout 500 --timeout-method thread ;;
     gpm)    run gpm 300 python -u -m pytest tests/test_gpu_model.py -q -rf --timeout 200 --timeout-method thread ;;
-    rccl)   run rccl 300 python bench.py --rccl --steps 20 --warmup 5 --no-cpu-baseline ;;  # the N > 1 collectives on one rank
+    rccl)   run rccl 300 python bench.py --full --rccl --steps 20 --warmup 5 --no-cpu-baseline ;;  # the N > 1 collectives on one rank
     gvstudy)  # GEMV study variants (build/variants/librcbf_gv*.so) vs the product, GP graph bench
       for n in prod ${GV_VARIANTS:-gv1 gv3 gvr128}; do
         if [ "$n" = prod ]; then lib=""; else lib="RCBF_HIP_LIB=build/variants/librcbf_$n.so"; fi

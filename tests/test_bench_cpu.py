@@ -96,6 +96,52 @@ def test_dry_run_line_carries_the_contract_fields(cfg):
     assert rf["bytes_per_env_step"] == {0: 241, 2: 253, 5: 68}[cfg]
 
 
+def test_full_is_off_by_default_and_implied_by_what_needs_it():
+    """A plain run measures the headline only; the roofline record and the
+    secondary rows are made of the --full measurements, so they switch it on."""
+    assert _args().full is False and _args("--gpus", "1", "--steps", "20", "--warmup", "5").full is False
+    assert _args("--full").full is True
+    assert _args("--record", "x.json").full is True and _args("--extra").full is True
+    assert _args().dump_outputs is None and _args("--dump-outputs", "d").dump_outputs == "d"
+
+
+def test_dry_run_line_says_whether_the_run_was_full():
+    for flags, want in (([], False), (["--full"], True)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-dry-run", "--steps", "4",
+                            "--warmup", "1", "--batch", "256", *flags], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["full"] is want and rec["steps"] == 4 and "cpu_baseline" not in rec
+
+
+def test_dump_outputs_files_dtypes_and_the_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per array, float64 kept, everything else as
+    float32, None skipped; beyond the byte cap the same seeded rows of every
+    array (their indices beside them), identical from call to call."""
+    import numpy as np
+    import torch
+    B = 1000
+    arrays = {"obs": torch.arange(B * 3, dtype=torch.float32).reshape(B, 3), "state": np.arange(B * 2, dtype=np.float64).reshape(B, 2),
+              "done": torch.arange(B, dtype=torch.uint8) % 2, "goal_met": None}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {p.name: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert sorted(got) == ["done.npy", "obs.npy", "state.npy"]
+    assert got["obs.npy"].dtype == np.float32 and got["state.npy"].dtype == np.float64 and got["done.npy"].dtype == np.float32
+    assert np.array_equal(got["obs.npy"], arrays["obs"].numpy()) and np.array_equal(got["done.npy"], np.arange(B) % 2)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)  # 12 + 16 + 4 B per row and 8 for its index: 100 rows
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    s1 = {p.name: np.load(p) for p in (tmp_path / "s1").iterdir()}
+    s2 = {p.name: np.load(p) for p in (tmp_path / "s2").iterdir()}
+    rows = s1["sample_rows.npy"].astype(np.int64)
+    assert len(rows) == 100 and len(set(rows)) == 100 and np.all(np.diff(rows) > 0) and rows.max() < B
+    assert sum(a.nbytes for a in s1.values()) <= 4000
+    assert np.array_equal(s1["state.npy"], arrays["state"][rows]) and np.array_equal(s1["obs.npy"], arrays["obs"].numpy()[rows])
+    assert sorted(s1) == sorted(s2) and all(np.array_equal(s1[k], s2[k]) for k in s1)
+    bench.dump_outputs(str(tmp_path / "ranked"), {"u": torch.zeros(4, 1)}, rank=1, world=2)
+    assert [p.name for p in (tmp_path / "ranked").iterdir()] == ["u_rank1.npy"]
+
+
 def test_rccl_flag_brings_up_the_group_on_one_rank():
     """bench.py --rccl on one rank runs the N > 1 path's process-group code (rendezvous on 127.0.0.1,
     barriers around the timed region, all_gather of the per-rank times, MAX all_reduce): over gloo in
