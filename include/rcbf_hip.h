@@ -539,8 +539,21 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
  * the buffers must stay allocated while the plan exists.  flags
  * RCBF_AQL_PROFILE: a completion signal per dispatch, read back with
  * rcbf_aql_plan_times (start, end in ns of the HSA system clock per step);
- * RCBF_AQL_PROFILE_ENDS: on the first and last dispatch only (the others
- * read back as 0).
+ * RCBF_AQL_PROFILE_ENDS: on the first and last dispatch only (the first
+ * dispatch's times in row 0, the last one's in row K - 1, the others 0).
+ *
+ * Two forms of a plan.  PER STEP: K dispatches of k_safe_step, one per step,
+ * an agent-scope fence between them.  FUSED: one dispatch of k_safe_steps
+ * per chunk of at most 4096 steps, in which the lane that owns env i runs
+ * all of env i's steps back to back; every step still stores everything a
+ * step stores, so memory ends up as K dispatches leave it, but nothing is
+ * re-loaded and no fence runs between steps.  The library builds the fused
+ * form when K > 1, the solver is the exact active set, span_out is NULL,
+ * none of RCBF_AQL_PROFILE, RCBF_AQL_STUDY_* and RCBF_AQL_PER_STEP is set,
+ * no u_RL buffer overlaps a buffer the steps write (the fused kernel loads
+ * the next step's action before the current step's stores), and the code
+ * object has the fused kernels; otherwise the per-step form.
+ * rcbf_aql_plan_dispatches: dispatch packets per run (K, or the chunks).
  * rcbf_aql_run: submit the K dispatches (barrier bit on each), ring the
  * doorbell once, busy-wait for completion; timeout_us 0 -> 10 s.  A plan
  * must not run after rcbf_aql_close of its queue (rcbf_aql_plan_free may
@@ -555,7 +568,9 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
 #define RCBF_AQL_STUDY_MID_NOACQ 16     /* STUDY ONLY: no acquire between steps */
 #define RCBF_AQL_STUDY_MID_NOREL 32     /* STUDY ONLY: no release between steps */
 #define RCBF_AQL_PROFILE_ENDS 64        /* timestamps of the first and the last dispatch only */
+#define RCBF_AQL_PER_STEP 128           /* build the per-step form (K dispatches) even where the fused form applies */
 #define RCBF_AQL_SAFE_STEP_KERNARG_BYTES 408 /* sizeof the k_safe_step argument block */
+#define RCBF_AQL_SAFE_STEPS_KERNARG_BYTES 408 /* sizeof the k_safe_steps (fused form) argument block */
 typedef struct rcbf_aql rcbf_aql;
 typedef struct rcbf_aql_plan rcbf_aql_plan;
 int rcbf_aql_open(int32_t device, const char* code_object, int32_t flags, rcbf_aql** out);
@@ -569,6 +584,7 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
                             uint64_t* span_out, int32_t flags, rcbf_aql_plan** out);
 int rcbf_aql_run(rcbf_aql_plan* plan, uint64_t timeout_us);
 int rcbf_aql_plan_times(const rcbf_aql_plan* plan, uint64_t* start_end_ns);
+int rcbf_aql_plan_dispatches(const rcbf_aql_plan* plan);
 int rcbf_aql_plan_free(rcbf_aql_plan* plan);
 
 /* ---------------------------------------------------------------------- */

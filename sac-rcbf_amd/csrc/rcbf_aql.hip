@@ -28,6 +28,17 @@
 // written by device work or copies that completed before the run (a system-
 // scope acquire there cost the first step ~3 us: profiles/r06/aql_fences_r06e.json).
 //
+// The fused form (r07).  A plan's actions are all known before it starts, and
+// env i at step j + 1 reads only what env i wrote at step j, so a plan of
+// K > 1 steps is ONE dispatch of rcbf::k_safe_steps (one per 4 096 steps) in
+// which each lane runs its env's steps back to back, every step storing
+// everything a step stores: the K - 1 fences and state re-loads between the
+// dispatches go away, memory ends up as K dispatches leave it.  When it
+// applies is decided in rcbf_aql_safe_step_plan; everything said above about
+// K packets describes the per-step form, which remains for K = 1, the other
+// solvers, span / per-dispatch-profiled / study plans, RCBF_AQL_PER_STEP and
+// action buffers that alias an output.
+//
 // Reference interface this serves: env.step() of the batched env inside the
 // SAC loop (main.py:93-95, sac_cbf.py:218-238) -- a synchronous call, like a
 // gym step: rcbf_aql_run returns when the K steps have completed.
@@ -46,8 +57,8 @@
 #include <string>
 #include <vector>
 
-#include "rcbf_common.hpp"
 #include "rcbf_hip.h"
+#include "rcbf_safe_step.hpp"  // SafeStepsArgs (the templates in it are not instantiated here)
 
 namespace {
 
@@ -90,6 +101,8 @@ static_assert(offsetof(SafeStepArgs, prm) == 152, "kernarg layout");
 static_assert(offsetof(SafeStepArgs, prior_cols) == 392, "kernarg layout");
 static_assert(offsetof(SafeStepArgs, stamp_buf) == 400, "kernarg layout");
 static_assert(sizeof(SafeStepArgs) == RCBF_AQL_SAFE_STEP_KERNARG_BYTES, "kernarg layout");
+// the fused form's kernel (rcbf::k_safe_steps) takes rcbf::SafeStepsArgs, defined next to it
+static_assert(sizeof(SafeStepsArgs) == RCBF_AQL_SAFE_STEPS_KERNARG_BYTES, "kernarg layout");
 
 struct KernelInfo {
     std::string name;  // mangled symbol without ".kd"
@@ -99,6 +112,7 @@ struct KernelInfo {
 
 constexpr uint32_t kQueueSize = 4096;  // packets (power of two); a plan longer than this is fed in chunks
 constexpr size_t kArgStride = 512;     // bytes per step's kernarg block (>= 408, 64-B multiple)
+constexpr int32_t kFusedChunk = (int32_t)kQueueSize;  // most steps one fused dispatch runs: a bounded kernel
 
 uint64_t now_ns() {
     timespec ts;
@@ -119,15 +133,17 @@ struct rcbf_aql {
     std::vector<KernelInfo> kernels;
     std::atomic<int> queue_error{0};
     int profiling = 0;
+    bool fused = false;  // the code object has the k_safe_steps kernels (the fused plan form)
 };
 
 struct rcbf_aql_plan {
     rcbf_aql* q = nullptr;
     int device = -1;  // the queue's HIP device (rcbf_aql_plan_free does not read q: a plan may outlive it)
-    int32_t K = 0;
-    void* kernargs = nullptr;                       // K * kArgStride bytes of device memory
+    int32_t K = 0;                                  // steps per run
+    void* kernargs = nullptr;                       // one kArgStride block per packet (+ the fused form's u_RL table)
     std::vector<hsa_kernel_dispatch_packet_t> pkt;  // pre-built packets (header written last, atomically)
-    std::vector<hsa_signal_t> sig;                  // completion signals: one per packet (profiled) or one
+    std::vector<hsa_signal_t> sig;                  // completion signals: one per packet (profiled), first and
+                                                    // last (ends; one if they are the same packet), or one
     int profiled = 0;
 };
 
@@ -192,6 +208,18 @@ std::string safe_step_prefix(int solver, int mode, int k, int bs, bool span) {
     snprintf(buf, sizeof buf, "_ZN4rcbf11k_safe_stepILi%dELi%dELi%dELb0ELi%dELb%dEEEv", solver, mode, k, bs,
              span ? 1 : 0);
     return buf;
+}
+
+// ... and of rcbf::k_safe_steps<MODE, K, BS> (SafeStepsArgs)
+std::string safe_steps_prefix(int mode, int k, int bs) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "_ZN4rcbf12k_safe_stepsILi%dELi%dELi%dEEEv", mode, k, bs);
+    return buf;
+}
+
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
 }
 
 const KernelInfo* find_kernel(const rcbf_aql* q, const std::string& prefix) {
@@ -292,13 +320,20 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe, q->agent, collect_kernel, q));
     // every k_safe_step instantiation in the code object must take exactly the
     // argument block SafeStepArgs describes
-    int n_steps = 0;
-    for (const auto& k : q->kernels)
+    // ... and every k_safe_steps instantiation SafeStepsArgs; a code object without them still opens, and
+    // its plans take the per-step form
+    int n_steps = 0, n_fused = 0;
+    for (const auto& k : q->kernels) {
         if (k.name.compare(0, 21, "_ZN4rcbf11k_safe_step") == 0) {
             ++n_steps;
             if (k.kernarg_bytes != sizeof(SafeStepArgs) || k.private_bytes != 0) rc = RCBF_E_BAD_SHAPE;
+        } else if (k.name.compare(0, 22, "_ZN4rcbf12k_safe_steps") == 0) {
+            ++n_fused;
+            if (k.kernarg_bytes != sizeof(SafeStepsArgs) || k.private_bytes != 0) rc = RCBF_E_BAD_SHAPE;
         }
+    }
     if (!rc && n_steps == 0) rc = RCBF_E_BAD_MODE;
+    q->fused = n_fused > 0;
     if (!rc)
         rc = hsa_rc(hsa_queue_create(q->agent, kQueueSize, HSA_QUEUE_TYPE_SINGLE, queue_error_cb, q, UINT32_MAX,
                                      UINT32_MAX, &q->queue));
@@ -352,13 +387,81 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
     if (!ki || ki->kernarg_bytes != sizeof(SafeStepArgs)) return RCBF_E_BAD_MODE;
     const uint64_t groups = (uint64_t)grid_for_envs(B, bs);
 
+    // The fused form: one dispatch of k_safe_steps per chunk of at most kFusedChunk steps, each lane running
+    // its env's steps back to back.  It needs the whole-plan view this call has (every action known before
+    // the run) and nothing per step from outside: no stamps, no per-dispatch timestamps, no study fences.
+    // The kernel loads step j + 1's action before step j's stores, so a u_RL buffer that overlaps anything
+    // the steps write keeps the plan in the per-step form (and its behaviour).
+    constexpr int32_t kPerStepFlags =
+        RCBF_AQL_PROFILE | RCBF_AQL_STUDY_MID_NOFENCE | RCBF_AQL_STUDY_MID_NOACQ | RCBF_AQL_STUDY_MID_NOREL |
+        RCBF_AQL_PER_STEP;
+    const KernelInfo* kf = nullptr;
+    if (q->fused && K > 1 && solver == RCBF_SOLVER_ACTIVE_SET && !span_out && !(flags & kPerStepFlags))
+        kf = find_kernel(q, safe_steps_prefix(mode, k, bs));
+    if (kf && kf->kernarg_bytes != sizeof(SafeStepsArgs)) kf = nullptr;
+    if (kf) {
+        const bool cars = mode == RCBF_MODE_SIMULATED_CARS;
+        const size_t ns = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NS : Dims<RCBF_MODE_UNICYCLE, 1>::NS;
+        const size_t no = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NO : Dims<RCBF_MODE_UNICYCLE, 1>::NO;
+        const size_t nu = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NU : Dims<RCBF_MODE_UNICYCLE, 1>::NU;
+        const size_t n = (size_t)B;
+        const struct {
+            const void* p;
+            size_t bytes;
+        } written[] = {{x, ns * n * 8},   {aux, n * 8},  {step, n * 4},     {episode, n * 4},
+                       {obs_out, no * n * 4}, {u_out, nu * n * 4}, {reward, n * 4}, {cost, n * 4},
+                       {done, n},          {goal_met, n}, {status_out, n * 4}, {fail_flag, 4}};
+        for (int32_t j = 0; j < n_u_rl && kf; ++j)
+            for (const auto& w : written)
+                if (overlaps(u_rl_seq[j], nu * n * 4, w.p, w.bytes)) {
+                    kf = nullptr;
+                    break;
+                }
+    }
+    const int32_t npkt = kf ? (K + kFusedChunk - 1) / kFusedChunk : K;
+
     auto* p = new rcbf_aql_plan();
     p->q = q;
     p->device = q->device;
     p->K = K;
     p->profiled = ends ? 2 : profiled ? 1 : 0;
-    std::vector<unsigned char> host((size_t)K * kArgStride, 0);
-    for (int32_t j = 0; j < K; ++j) {
+    // the fused form's table of the n_u_rl action pointers follows the argument blocks
+    const size_t table_off = (size_t)npkt * kArgStride;
+    std::vector<unsigned char> host(table_off + (kf ? (size_t)n_u_rl * sizeof(const float*) : 0), 0);
+    int rc = (int)hipMalloc(&p->kernargs, host.size());
+    if (kf) std::memcpy(host.data() + table_off, u_rl_seq, (size_t)n_u_rl * sizeof(const float*));
+    for (int32_t j = 0; j < npkt && !rc; ++j) {
+        if (kf) {
+            SafeStepsArgs a;
+            std::memset(&a, 0, sizeof a);
+            a.B = B;
+            a.x = x;
+            a.aux = aux;
+            a.step = step;
+            a.u_tab = reinterpret_cast<const float* const*>(static_cast<unsigned char*>(p->kernargs) + table_off);
+            a.episode = episode;
+            a.mu = mu;
+            a.sigma = sigma;
+            a.obs_out = obs_out;
+            a.u_out = u_out;
+            a.reward = reward;
+            a.cost = cost;
+            a.done = done;
+            a.goal_met = goal_met;
+            a.status_out = status_out;
+            a.fail_flag = fail_flag;
+            a.auto_reset = auto_reset;
+            a.seed = seed;
+            a.off = env_offset;
+            a.prm = *prm;
+            a.prior_cols = prior_cols ? 1 : 0;
+            a.n_u = n_u_rl;
+            // chunk j: steps j kFusedChunk ... of the plan; its first step reads u_rl_seq[that index % n_u_rl]
+            a.steps = std::min<int32_t>(kFusedChunk, K - j * kFusedChunk);
+            a.ju0 = (int32_t)(((int64_t)j * kFusedChunk) % n_u_rl);
+            std::memcpy(host.data() + (size_t)j * kArgStride, &a, sizeof a);
+            continue;
+        }
         SafeStepArgs a;
         std::memset(&a, 0, sizeof a);
         a.B = B;
@@ -387,9 +490,10 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
                                : nullptr;
         std::memcpy(host.data() + (size_t)j * kArgStride, &a, sizeof a);
     }
-    int rc = (int)hipMalloc(&p->kernargs, host.size());
     if (!rc) rc = (int)hipMemcpy(p->kernargs, host.data(), host.size(), hipMemcpyHostToDevice);
-    const int nsig = p->profiled == 1 ? K : p->profiled == 2 ? 2 : 1;
+    // ends: a signal on the first and on the last packet; when they are the same packet, one signal is both
+    // (with two, the last one is on no packet and rcbf_aql_run would wait for it until its timeout)
+    const int nsig = p->profiled == 1 ? npkt : p->profiled == 2 ? (npkt > 1 ? 2 : 1) : 1;
     for (int j = 0; !rc && j < nsig; ++j) {
         hsa_signal_t s;
         rc = hsa_rc(hsa_signal_create(1, 0, nullptr, &s));
@@ -399,14 +503,17 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
         rcbf_aql_plan_free(p);
         return rc;
     }
-    p->pkt.resize(K);
-    for (int32_t j = 0; j < K; ++j) {
+    const KernelInfo* kd = kf ? kf : ki;
+    p->pkt.resize(npkt);
+    for (int32_t j = 0; j < npkt; ++j) {
         hsa_kernel_dispatch_packet_t& d = p->pkt[j];
         std::memset(&d, 0, sizeof d);
         int acq = j == 0 && (flags & RCBF_AQL_FIRST_ACQUIRE_SYSTEM) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
-        int rel = j == K - 1 && !(flags & RCBF_AQL_LAST_RELEASE_AGENT) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
+        int rel =
+            j == npkt - 1 && !(flags & RCBF_AQL_LAST_RELEASE_AGENT) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
         if ((flags & (RCBF_AQL_STUDY_MID_NOFENCE | RCBF_AQL_STUDY_MID_NOACQ)) && j > 0) acq = HSA_FENCE_SCOPE_NONE;
-        if ((flags & (RCBF_AQL_STUDY_MID_NOFENCE | RCBF_AQL_STUDY_MID_NOREL)) && j < K - 1) rel = HSA_FENCE_SCOPE_NONE;
+        if ((flags & (RCBF_AQL_STUDY_MID_NOFENCE | RCBF_AQL_STUDY_MID_NOREL)) && j < npkt - 1)
+            rel = HSA_FENCE_SCOPE_NONE;
         d.header = (uint16_t)((HSA_PACKET_TYPE_KERNEL_DISPATCH << HSA_PACKET_HEADER_TYPE) |
                               (1 << HSA_PACKET_HEADER_BARRIER) | (acq << HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) |
                               (rel << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE));
@@ -417,15 +524,15 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
         d.grid_size_x = (uint32_t)(groups * (uint64_t)bs);
         d.grid_size_y = 1;
         d.grid_size_z = 1;
-        d.private_segment_size = ki->private_bytes;
-        d.group_segment_size = ki->group_bytes;
-        d.kernel_object = ki->object;
+        d.private_segment_size = kd->private_bytes;
+        d.group_segment_size = kd->group_bytes;
+        d.kernel_object = kd->object;
         d.kernarg_address = static_cast<unsigned char*>(p->kernargs) + (size_t)j * kArgStride;
         if (p->profiled == 1)
             d.completion_signal = p->sig[j];
-        else if (p->profiled == 2 && (j == 0 || j == K - 1))
-            d.completion_signal = p->sig[j == 0 ? 0 : 1];
-        else if (j == K - 1)
+        else if (p->profiled == 2 && (j == 0 || j == npkt - 1))
+            d.completion_signal = j == 0 ? p->sig.front() : p->sig.back();
+        else if (j == npkt - 1)
             d.completion_signal = p->sig[0];
         else
             d.completion_signal.handle = 0;
@@ -448,7 +555,7 @@ int32_t feed(rcbf_aql_plan* p, int32_t j) {
     const uint64_t wr = hsa_queue_load_write_index_relaxed(queue);
     const uint64_t room = queue->size - (wr - rd);
     if (room == 0) return j;
-    const int32_t n = (int32_t)std::min<uint64_t>(room, (uint64_t)(p->K - j));
+    const int32_t n = (int32_t)std::min<uint64_t>(room, (uint64_t)((int32_t)p->pkt.size() - j));
     const uint64_t w = hsa_queue_add_write_index_relaxed(queue, (uint64_t)n);
     for (int32_t i = 0; i < n; ++i) {
         hsa_kernel_dispatch_packet_t* slot = &ring[(w + i) & mask];
@@ -483,9 +590,9 @@ int rcbf_aql_run(rcbf_aql_plan* p, uint64_t timeout_us) {
     if (p->q->queue_error.load()) return RCBF_E_HSA;
     for (auto& s : p->sig) hsa_signal_store_relaxed(s, 1);
     const uint64_t t_end = now_ns() + (timeout_us ? timeout_us : 10000000ull) * 1000ull;
-    // as many packets as the ring has room for (all of them unless K > the ring), then the rest as the
-    // packet processor frees slots
-    for (int32_t j = 0; j < p->K;) {
+    // as many packets as the ring has room for (all of them unless there are more than the ring holds),
+    // then the rest as the packet processor frees slots
+    for (int32_t j = 0, n = (int32_t)p->pkt.size(); j < n;) {
         const int32_t nj = feed(p, j);
         if (nj == j) {
             if (p->q->queue_error.load()) return RCBF_E_HSA;
@@ -505,18 +612,24 @@ int rcbf_aql_plan_times(const rcbf_aql_plan* p, uint64_t* start_end_ns) {
     if (!freq) return RCBF_E_HSA;
     for (int32_t j = 0; j < p->K; ++j) {
         hsa_amd_profiling_dispatch_time_t t;
-        int si = j;
-        if (p->profiled == 2) {  // only the first and the last packets carry a signal
+        hsa_signal_t sg;
+        if (p->profiled == 2) {
+            // only the first and the last packet carry a signal: the first packet's times in row 0, the
+            // last packet's in row K - 1 (one packet, fused or K = 1: both rows are that packet's)
             start_end_ns[2 * j] = start_end_ns[2 * j + 1] = 0;
             if (j != 0 && j != p->K - 1) continue;
-            si = j == 0 ? 0 : 1;
+            sg = j == 0 ? p->sig.front() : p->sig.back();
+        } else {
+            sg = p->sig[j];  // a per-dispatch profile is always the per-step form: packet j is step j
         }
-        if (hsa_amd_profiling_get_dispatch_time(p->q->agent, p->sig[si], &t) != HSA_STATUS_SUCCESS) return RCBF_E_HSA;
+        if (hsa_amd_profiling_get_dispatch_time(p->q->agent, sg, &t) != HSA_STATUS_SUCCESS) return RCBF_E_HSA;
         start_end_ns[2 * j] = (uint64_t)((long double)t.start * 1e9L / (long double)freq);
         start_end_ns[2 * j + 1] = (uint64_t)((long double)t.end * 1e9L / (long double)freq);
     }
     return 0;
 }
+
+int rcbf_aql_plan_dispatches(const rcbf_aql_plan* p) { return p ? (int)p->pkt.size() : RCBF_E_NULL; }
 
 int rcbf_aql_plan_free(rcbf_aql_plan* p) {
     if (!p) return 0;

@@ -8,6 +8,20 @@
 
 using namespace rcbf;
 
+// The K-steps-per-dispatch kernels of the AQL plan's fused form (csrc/rcbf_aql.hip dispatches them from
+// librcbf_steps.co; no HIP launch uses them): cars, and the unicycle at 1 .. RCBF_MAX_HAZARDS hazards.
+namespace rcbf {
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_SIMULATED_CARS, 1);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 1);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 2);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 3);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 4);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 5);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 6);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 7);
+RCBF_SAFE_STEPS_INSTANTIATE(RCBF_MODE_UNICYCLE, 8);
+}  // namespace rcbf
+
 namespace {
 
 template <int MODE>

@@ -11,6 +11,8 @@
 // on resets.
 #pragma once
 
+#include <cstddef>
+
 #include "rcbf_common.hpp"
 
 // study override: prefetch this many argument lines in every mode
@@ -102,9 +104,8 @@ __device__ __forceinline__ void store_obs32(float* obs, int64_t i, const double*
 // would otherwise hold each following LDS read (and its wait) behind the
 // previous store.
 template <int MODE, bool WT = false>
-__device__ __forceinline__ void store_obs_chunks(float* obs, int64_t base, const float* lds_wave) {
+__device__ __forceinline__ void store_obs_chunks(float* obs, int64_t base, const float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
-    const int lane = threadIdx.x & 63;
     __builtin_amdgcn_wave_barrier();
     constexpr int CH = NO * 16;  // 16-byte chunks in the wave's block
     const float4* src = reinterpret_cast<const float4*>(lds_wave);
@@ -130,9 +131,8 @@ __device__ __forceinline__ void store_obs_chunks(float* obs, int64_t base, const
 // strided dwordx2).  Partial or unaligned waves take the per-lane path.
 template <int MODE, bool WT = false>
 __device__ __forceinline__ void store_obs32_staged(float* obs, int64_t i, int64_t B, const double* xs,
-                                                   const double* obs_cache, float* lds_wave) {
+                                                   const double* obs_cache, float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
-    const int lane = threadIdx.x & 63;
     const int64_t base = i - lane;
 #ifdef RCBF_STUDY_EPW  // study: a 64-thread workgroup's wave holds fewer than 64 envs (per-lane stores)
     const bool full = blockDim.x != 64 && (base + 64 <= B) && ((reinterpret_cast<uintptr_t>(obs) & 15) == 0);
@@ -160,106 +160,37 @@ __device__ __forceinline__ void store_obs32_staged(float* obs, int64_t i, int64_
 #pragma unroll
         for (int k = 0; k < NO; ++k) lds_wave[lane * NO + k] = (float)o[k];
     }
-    store_obs_chunks<MODE, WT>(obs, base, lds_wave);
+    store_obs_chunks<MODE, WT>(obs, base, lds_wave, lane);
 }
 
-// The fused safe step (rcbf_safe_step): one env per lane.  ST = true only in
-// the study build (csrc/study/rcbf_stamps.hip), which records phase
-// timestamps into `stamps`; the product instantiation ignores it.
-// BS: workgroup size (block_for_envs).  SPAN = true (rcbf_safe_step_span, a
-// measurement entry point of the product library): lane 0 of every wave
-// writes the chip clock (s_memrealtime, 100 MHz) at its start and after its
-// own stores have completed to stamp_buf[4 w], [4 w + 1], and the shader
-// clock (s_memtime) at the same two points to stamp_buf[4 w + 2], [4 w + 3]
-// (the clock the wave ran at is delta(s_memtime) / delta(s_memrealtime) x
-// 100 MHz); every other instruction is the product's.
-// Argument order: B and the pointers of the first loads lead (one 64-B line
-// of the argument block, which the launch can preload into SGPRs), the
-// parameter block comes last.
-template <int SOLVER, int MODE, int K, bool ST = false, int BS = kBlock, bool SPAN = false>
-__global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict__ x, double* __restrict__ aux,
-                                                      int32_t* __restrict__ step, const float* __restrict__ u_rl,
-                                                      uint32_t* __restrict__ episode, const float* __restrict__ mu,
-                                                      const float* __restrict__ sigma, float* __restrict__ obs_out,
-                                                      float* __restrict__ u_out, float* __restrict__ reward,
-                                                      float* __restrict__ cost, uint8_t* __restrict__ done,
-                                                      uint8_t* __restrict__ goal_met,
-                                                      int32_t* __restrict__ status_out, int32_t* fail_flag,
-                                                      int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
-                                                      int prior_cols = 0, unsigned long long* stamp_buf = nullptr) {
+// One fused safe step of env i, from its state and inputs in registers (xs, a,
+// st, us, m, s; ep_pre / ep0: the episode counter loaded ahead, see
+// reset_foreseeable) to every store a step makes: the state pairs, aux, step,
+// the episode counter on a reset, the observation (staged through obs_stage,
+// this wave's 64 x NO floats of LDS; lane: threadIdx.x & 63), u, reward, cost, done, goal_met, the
+// status and the fail_flag OR.  xs, a and st come back as the post-step state.
+// Shared by k_safe_step (one step per dispatch) and k_safe_steps (K steps per
+// dispatch): one source for both.  wt_lds: the write-through staging block of
+// the RCBF_WT_OUT study build.
+template <int SOLVER, int MODE, int K, bool ST, bool WT>
+__device__ __forceinline__ void safe_step_body(
+    const rcbf_params& prm, int64_t B, int64_t i, double* __restrict__ x, double* __restrict__ aux,
+    int32_t* __restrict__ step, uint32_t* __restrict__ episode, float* __restrict__ obs_out,
+    float* __restrict__ u_out, float* __restrict__ reward, float* __restrict__ cost, uint8_t* __restrict__ done,
+    uint8_t* __restrict__ goal_met, int32_t* __restrict__ status_out, int32_t* fail_flag, int auto_reset,
+    uint64_t seed, int64_t off, double* xs, double& a, int& st, const float* us, const float* m, const float* s,
+    bool ep_pre, uint32_t ep0, const Stamps<ST>& stamps, float* obs_stage, char* wt_lds, int lane) {
     using D = Dims<MODE, K>;
-    // RCBF_WT_OUT: every output write-through, the wave's stores drained before
-    // it ends (rcbf_common.hpp, WtStage); the study stamps build keeps the nt form
-    constexpr bool WT = RCBF_WT_OUT != 0 && !ST;
-    int64_t i = env_index<BS>();
-    if (i >= B) return;
-    const int lane = threadIdx.x & 63;
     const int64_t wbase = i - lane;
     const bool wfull = wbase + 64 <= B;  // wave-uniform: every lane of this wave is live
-    constexpr int kWtBytes = WT ? 16 * 160 : 16;  // per wave: the largest WtStage below (unicycle, 152 chunks)
-    __shared__ __attribute__((aligned(16))) char wt_lds_all[BS / 64][kWtBytes];
-    char* wt_lds = wt_lds_all[threadIdx.x >> 6];
+    constexpr int kWtBytes = WT ? 16 * 160 : 16;  // the caller's per-wave wt_lds block
     (void)wt_lds;
     (void)wfull;
-    unsigned long long span_t0 = 0, span_c0 = 0;
-    if constexpr (SPAN) {
-        span_t0 = __builtin_amdgcn_s_memrealtime();
-        span_c0 = __builtin_amdgcn_s_memtime();
-    }
-    Stamps<ST> stamps;
-    stamps.buf = stamp_buf;
-    stamps.mark(0, false);
-    double xs[D::NS];
-    load_state<MODE>(x, B, i, xs);
-    double a = ld_in(&aux[i]);
-    int st = ld_in(&step[i]);
-    float us[D::NU], m[D::NS], s[D::NS], uf[D::NU];
-#pragma unroll
-    for (int c = 0; c < D::NU; ++c) us[c] = ld_in(&u_rl[i * D::NU + c]);
-#if RCBF_KARG_PREFETCH
-    prefetch_kernargs<RCBF_KARG_PREFETCH>();
-#else
-    // cars: 3.87 -> 3.81 us per step; the unicycle step is slower with it
-    // (4.38 -> 4.50 us at k = 5; profiles/r03/kernarg_preload_ab_r03d.txt)
-    if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) prefetch_kernargs<7>();
-#endif
-    const bool ep_pre = episode && reset_foreseeable<MODE>(st, a);
-    uint32_t ep0 = 0;
-    if (ep_pre) ep0 = episode[i];
-    if (prior_cols) {
-        // column layout (rcbf_safe_step_cols): only what the rows read, one
-        // contiguous (B,) f32 column each -- cars sigma (3, B) = sigma[:, 5],
-        // [:, 7], [:, 9] (the cars rows ignore mu, diff_cbf_qp.py:298-299);
-        // unicycle mu and sigma (3, B)
-#pragma unroll
-        for (int k = 0; k < D::NS; ++k) {
-            m[k] = 0.0f;
-            s[k] = prior_sigma<MODE>(k);
-        }
-        if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) {
-            if (sigma) {
-                s[5] = ld_in(&sigma[i]);
-                s[7] = ld_in(&sigma[B + i]);
-                s[9] = ld_in(&sigma[2 * B + i]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < D::NS; ++k) {
-                if (mu) m[k] = ld_in(&mu[k * B + i]);
-                if (sigma) s[k] = ld_in(&sigma[k * B + i]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < D::NS; ++k) {
-            m[k] = mu ? mu[i * D::NS + k] : 0.0f;
-            s[k] = sigma ? sigma[i * D::NS + k] : prior_sigma<MODE>(k);
-        }
-    }
+    (void)kWtBytes;
     float rew, cst;
     bool dn, gm;
     int status;
-    stamps.mark(1, true);
+    float uf[D::NU];
     double oc[4] = {0.0, 0.0, 0.0, 0.0};
     if constexpr (MODE == RCBF_MODE_SIMULATED_CARS && RCBF_EARLY_STORE && !ST) {
         // The same step in an order that lets 76 of the 145 written bytes
@@ -330,8 +261,7 @@ __global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict_
             st_out(&step[i], st);
         }
     }
-    __shared__ float obs_stage[BS / 64][64 * D::NO];
-    store_obs32_staged<MODE, WT>(obs_out, i, B, xs, oc, obs_stage[threadIdx.x >> 6]);
+    store_obs32_staged<MODE, WT>(obs_out, i, B, xs, oc, obs_stage, lane);
     if constexpr (WT) {
         constexpr int NU4 = 4 * D::NU;
         float ufc[D::NU];
@@ -391,6 +321,102 @@ __global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict_
     } else {
         report(status, status_out, i, fail_flag);
     }
+}
+
+// The fused safe step (rcbf_safe_step): one env per lane.  ST = true only in
+// the study build (csrc/study/rcbf_stamps.hip), which records phase
+// timestamps into `stamps`; the product instantiation ignores it.
+// BS: workgroup size (block_for_envs).  SPAN = true (rcbf_safe_step_span, a
+// measurement entry point of the product library): lane 0 of every wave
+// writes the chip clock (s_memrealtime, 100 MHz) at its start and after its
+// own stores have completed to stamp_buf[4 w], [4 w + 1], and the shader
+// clock (s_memtime) at the same two points to stamp_buf[4 w + 2], [4 w + 3]
+// (the clock the wave ran at is delta(s_memtime) / delta(s_memrealtime) x
+// 100 MHz); every other instruction is the product's.
+// Argument order: B and the pointers of the first loads lead (one 64-B line
+// of the argument block, which the launch can preload into SGPRs), the
+// parameter block comes last.
+template <int SOLVER, int MODE, int K, bool ST = false, int BS = kBlock, bool SPAN = false>
+__global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict__ x, double* __restrict__ aux,
+                                                      int32_t* __restrict__ step, const float* __restrict__ u_rl,
+                                                      uint32_t* __restrict__ episode, const float* __restrict__ mu,
+                                                      const float* __restrict__ sigma, float* __restrict__ obs_out,
+                                                      float* __restrict__ u_out, float* __restrict__ reward,
+                                                      float* __restrict__ cost, uint8_t* __restrict__ done,
+                                                      uint8_t* __restrict__ goal_met,
+                                                      int32_t* __restrict__ status_out, int32_t* fail_flag,
+                                                      int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
+                                                      int prior_cols = 0, unsigned long long* stamp_buf = nullptr) {
+    using D = Dims<MODE, K>;
+    // RCBF_WT_OUT: every output write-through, the wave's stores drained before
+    // it ends (rcbf_common.hpp, WtStage); the study stamps build keeps the nt form
+    constexpr bool WT = RCBF_WT_OUT != 0 && !ST;
+    int64_t i = env_index<BS>();
+    if (i >= B) return;
+    constexpr int kWtBytes = WT ? 16 * 160 : 16;  // per wave: the largest WtStage of the body (unicycle, 152 chunks)
+    __shared__ __attribute__((aligned(16))) char wt_lds_all[BS / 64][kWtBytes];
+    char* wt_lds = wt_lds_all[threadIdx.x >> 6];
+    unsigned long long span_t0 = 0, span_c0 = 0;
+    if constexpr (SPAN) {
+        span_t0 = __builtin_amdgcn_s_memrealtime();
+        span_c0 = __builtin_amdgcn_s_memtime();
+    }
+    Stamps<ST> stamps;
+    stamps.buf = stamp_buf;
+    stamps.mark(0, false);
+    double xs[D::NS];
+    load_state<MODE>(x, B, i, xs);
+    double a = ld_in(&aux[i]);
+    int st = ld_in(&step[i]);
+    float us[D::NU], m[D::NS], s[D::NS];
+#pragma unroll
+    for (int c = 0; c < D::NU; ++c) us[c] = ld_in(&u_rl[i * D::NU + c]);
+#if RCBF_KARG_PREFETCH
+    prefetch_kernargs<RCBF_KARG_PREFETCH>();
+#else
+    // cars: 3.87 -> 3.81 us per step; the unicycle step is slower with it
+    // (4.38 -> 4.50 us at k = 5; profiles/r03/kernarg_preload_ab_r03d.txt)
+    if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) prefetch_kernargs<7>();
+#endif
+    const bool ep_pre = episode && reset_foreseeable<MODE>(st, a);
+    uint32_t ep0 = 0;
+    if (ep_pre) ep0 = episode[i];
+    if (prior_cols) {
+        // column layout (rcbf_safe_step_cols): only what the rows read, one
+        // contiguous (B,) f32 column each -- cars sigma (3, B) = sigma[:, 5],
+        // [:, 7], [:, 9] (the cars rows ignore mu, diff_cbf_qp.py:298-299);
+        // unicycle mu and sigma (3, B)
+#pragma unroll
+        for (int k = 0; k < D::NS; ++k) {
+            m[k] = 0.0f;
+            s[k] = prior_sigma<MODE>(k);
+        }
+        if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) {
+            if (sigma) {
+                s[5] = ld_in(&sigma[i]);
+                s[7] = ld_in(&sigma[B + i]);
+                s[9] = ld_in(&sigma[2 * B + i]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < D::NS; ++k) {
+                if (mu) m[k] = ld_in(&mu[k * B + i]);
+                if (sigma) s[k] = ld_in(&sigma[k * B + i]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < D::NS; ++k) {
+            m[k] = mu ? mu[i * D::NS + k] : 0.0f;
+            s[k] = sigma ? sigma[i * D::NS + k] : prior_sigma<MODE>(k);
+        }
+    }
+    stamps.mark(1, true);
+    __shared__ float obs_stage[BS / 64][64 * D::NO];
+    safe_step_body<SOLVER, MODE, K, ST, WT>(prm, B, i, x, aux, step, episode, obs_out, u_out, reward, cost, done,
+                                            goal_met, status_out, fail_flag, auto_reset, seed, off, xs, a, st, us, m,
+                                            s, ep_pre, ep0, stamps, obs_stage[threadIdx.x >> 6], wt_lds,
+                                            threadIdx.x & 63);
     stamps.mark(7, true);
     if constexpr (SPAN) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have landed
@@ -404,5 +430,206 @@ __global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict_
         }
     }
 }
+
+// Argument block of k_safe_steps, at the offsets of its parameter list (the
+// AMDGPU kernarg ABI: every argument at its natural alignment): k_safe_step's
+// block with the u_RL table in u_rl's place and n_u, steps, ju0 in the stamp
+// pointer's.  The plan builder (csrc/rcbf_aql.hip) writes it; rcbf_aql_open and
+// tests/test_abi_fused_cpu.py check it against the code object.
+struct SafeStepsArgs {
+    int64_t B;
+    double* x;
+    double* aux;
+    int32_t* step;
+    const float* const* u_tab;
+    uint32_t* episode;
+    const float* mu;
+    const float* sigma;
+    float* obs_out;
+    float* u_out;
+    float* reward;
+    float* cost;
+    uint8_t* done;
+    uint8_t* goal_met;
+    int32_t* status_out;
+    int32_t* fail_flag;
+    int32_t auto_reset;
+    uint64_t seed;
+    int64_t off;
+    rcbf_params prm;
+    int32_t prior_cols;
+    int32_t n_u;
+    int32_t steps;
+    int32_t ju0;
+};
+static_assert(offsetof(SafeStepsArgs, auto_reset) == 128 && offsetof(SafeStepsArgs, seed) == 136 &&
+                  offsetof(SafeStepsArgs, prm) == 152 && offsetof(SafeStepsArgs, prior_cols) == 392 &&
+                  offsetof(SafeStepsArgs, n_u) == 396 && offsetof(SafeStepsArgs, steps) == 400 &&
+                  offsetof(SafeStepsArgs, ju0) == 404 && sizeof(SafeStepsArgs) == 408,
+              "kernarg layout");
+
+// K consecutive fused safe steps of a plan in ONE dispatch (the fused form of
+// rcbf_aql_safe_step_plan): the lane that owns env i runs all `steps` steps of
+// env i.  Env i at step j + 1 reads only what env i wrote at step j, its own
+// u_RL element and the priors, so no step needs anything another lane, wave or
+// XCD produced, and neither the fence between two dispatches nor the re-load
+// of x, aux, step is needed.  Every step still makes every store a k_safe_step
+// dispatch makes (safe_step_body), so after the dispatch HBM holds what
+// `steps` dispatches leave.  Step j reads u_tab[(ju0 + j) % n_u]: u_tab is a
+// table of n_u device pointers in device memory, ju0 < n_u.  The u_RL buffers
+// must not overlap anything the steps write (the next step's action is loaded
+// before this step's stores; the plan builder checks it).  Same grid,
+// workgroup size and lane-to-env map as k_safe_step; the exact solver only.
+// The argument block (SafeStepsArgs above) keeps k_safe_step's offsets, with
+// the table in u_rl's place.
+template <int MODE, int K, int BS = kBlock>
+__global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict__ x, double* __restrict__ aux,
+                                                       int32_t* __restrict__ step,
+                                                       const float* const* __restrict__ u_tab,
+                                                       uint32_t* __restrict__ episode, const float* __restrict__ mu,
+                                                       const float* __restrict__ sigma, float* __restrict__ obs_out,
+                                                       float* __restrict__ u_out, float* __restrict__ reward,
+                                                       float* __restrict__ cost, uint8_t* __restrict__ done,
+                                                       uint8_t* __restrict__ goal_met,
+                                                       int32_t* __restrict__ status_out, int32_t* fail_flag,
+                                                       int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
+                                                       int prior_cols, int n_u, int steps, int ju0) {
+    using D = Dims<MODE, K>;
+    constexpr int SOLVER = RCBF_SOLVER_ACTIVE_SET;
+    constexpr bool WT = false;
+    int64_t i = env_index<BS>();
+    if (i >= B) return;
+    double xs[D::NS];
+    load_state<MODE>(x, B, i, xs);
+    double a = ld_in(&aux[i]);
+    int st = ld_in(&step[i]);
+    int ju = ju0;
+    float us[D::NU], m[D::NS], s[D::NS];
+    {
+        const float* __restrict__ u0 = u_tab[ju];
+#pragma unroll
+        for (int c = 0; c < D::NU; ++c) us[c] = ld_in(&u0[i * D::NU + c]);
+    }
+    if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) prefetch_kernargs<7>();
+    // the priors: inputs of the plan that nothing in a run writes, loaded once (k_safe_step's layouts)
+    if (prior_cols) {
+#pragma unroll
+        for (int k = 0; k < D::NS; ++k) {
+            m[k] = 0.0f;
+            s[k] = prior_sigma<MODE>(k);
+        }
+        if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) {
+            if (sigma) {
+                s[5] = ld_in(&sigma[i]);
+                s[7] = ld_in(&sigma[B + i]);
+                s[9] = ld_in(&sigma[2 * B + i]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < D::NS; ++k) {
+                if (mu) m[k] = ld_in(&mu[k * B + i]);
+                if (sigma) s[k] = ld_in(&sigma[k * B + i]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < D::NS; ++k) {
+            m[k] = mu ? mu[i * D::NS + k] : 0.0f;
+            s[k] = sigma ? sigma[i * D::NS + k] : prior_sigma<MODE>(k);
+        }
+    }
+    __shared__ float obs_stage[BS / 64][64 * D::NO];
+    const Stamps<false> stamps{};
+    // Register budget of the loop.  Whatever the body derives from loop-invariant values alone (null
+    // tests and per-lane addresses of the 15 buffers, the 60 dwords of the parameter block, the loop's
+    // own counters) the compiler hoists out of the loop, where it stays live over the whole body on top
+    // of what one step needs -- and the unicycle step alone takes every scalar register there is, and
+    // at 7 and 8 hazards every vector register.  So everything the loop carries beside the env's state
+    // lives in accumulation registers (the unified file has room there: 230 of 256 used at k = 8), as
+    // uniform per-lane values behind empty asm copies the compiler cannot see through; no instruction
+    // is emitted for a copy, a use costs one register read.  Every step then derives from them what
+    // k_safe_step derives once per dispatch, and the parameter block is read from the argument segment
+    // again (scalar loads that hit the scalar cache; vector loads at k = 8).  No kernel spills.
+    int64_t Bv = B;
+    double* xv = x;
+    double* auxv = aux;
+    int32_t* stepv = step;
+    uint32_t* epv = episode;
+    float* obsv = obs_out;
+    float* uv = u_out;
+    float* rewv = reward;
+    float* costv = cost;
+    uint8_t* donev = done;
+    uint8_t* goalv = goal_met;
+    int32_t* statv = status_out;
+    int32_t* failv = fail_flag;
+    const float* const* tabv = u_tab;
+    int arv = auto_reset, lanev = threadIdx.x & 63, nuv = n_u, juv = ju, leftv = steps,
+        widv = threadIdx.x >> 6;
+    uint64_t seedv = seed;
+    int64_t offv = off;
+#define RCBF_OPAQUE_V()                                                                                         \
+    asm volatile("" : "+a"(xv), "+a"(auxv), "+a"(stepv), "+a"(epv), "+a"(obsv), "+a"(uv), "+a"(rewv));        \
+    asm volatile("" : "+a"(costv), "+a"(donev), "+a"(goalv), "+a"(statv), "+a"(failv), "+a"(tabv), "+a"(Bv), \
+                 "+a"(arv), "+a"(lanev), "+a"(i));                                                              \
+    asm volatile("" : "+a"(widv), "+a"(nuv), "+a"(juv), "+a"(leftv), "+a"(seedv), "+a"(offv))
+    RCBF_OPAQUE_V();  // once: uniform values, kept in accumulation registers from here on
+#pragma nounroll
+    while (leftv > 0) {
+        RCBF_OPAQUE_V();  // every step: nothing derived from them is loop-invariant to the compiler
+#pragma unroll
+        for (int k = 0; k < D::NS; ++k) asm volatile("" : "+a"(m[k]), "+a"(s[k]));  // the priors too
+        const rcbf_params* prm_p = &prm;
+        if constexpr (K >= 8) {
+            // k = 8: the step's scalar registers are all taken, so its parameters come through vector loads
+            // (the block's address in the argument segment, as a per-lane value)
+            prm_p = reinterpret_cast<const rcbf_params*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                         offsetof(SafeStepsArgs, prm));
+            asm volatile("" : "+v"(prm_p));
+        } else {
+            uint32_t prm_off = 0;
+            asm volatile("" : "+s"(prm_off));
+            prm_p = reinterpret_cast<const rcbf_params*>(reinterpret_cast<const char*>(&prm) + prm_off);
+        }
+        const rcbf_params& prm_j = *prm_p;
+        // the next step's action, issued ahead of this step's chain
+        float un[D::NU];
+#pragma unroll
+        for (int c = 0; c < D::NU; ++c) un[c] = 0.0f;
+        --leftv;
+        if (leftv > 0) {
+            juv = juv + 1 == nuv ? 0 : juv + 1;
+            const float* __restrict__ u1 = tabv[juv];
+#pragma unroll
+            for (int c = 0; c < D::NU; ++c) un[c] = ld_in(&u1[i * D::NU + c]);
+        }
+        // the counter this lane itself stored at its last reset, re-read only when a reset is foreseeable
+        const bool ep_pre = epv && reset_foreseeable<MODE>(st, a);
+        uint32_t ep0 = 0;
+        if (ep_pre) ep0 = epv[i];
+        safe_step_body<SOLVER, MODE, K, false, WT>(prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv, costv, donev,
+                                                   goalv, statv, failv, arv, seedv, offv, xs, a, st, us, m, s,
+                                                   ep_pre, ep0, stamps, obs_stage[widv], nullptr, lanev);
+        // this step's chunk reads of obs_stage stay ahead of the next step's writes to it (one wave's LDS
+        // operations execute in order; this keeps the compiler from reordering them)
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int c = 0; c < D::NU; ++c) us[c] = un[c];
+    }
+#undef RCBF_OPAQUE_V
+}
+
+// Explicit instantiation of k_safe_steps for every mode / hazard count and
+// workgroup size k_safe_step has (used once, by rcbf_env.hip): 27 kernels.
+#define RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, BS_)                                                              \
+    template __global__ void k_safe_steps<MODE_, K_, BS_>(                                                          \
+        int64_t, double* __restrict__, double* __restrict__, int32_t* __restrict__, const float* const* __restrict__, \
+        uint32_t* __restrict__, const float* __restrict__, const float* __restrict__, float* __restrict__,          \
+        float* __restrict__, float* __restrict__, float* __restrict__, uint8_t* __restrict__, uint8_t* __restrict__, \
+        int32_t* __restrict__, int32_t*, int, uint64_t, int64_t, rcbf_params, int, int, int, int)
+#define RCBF_SAFE_STEPS_INSTANTIATE(MODE_, K_)      \
+    RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, 64);  \
+    RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, 128); \
+    RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, 256)
 
 }  // namespace rcbf

@@ -124,6 +124,7 @@ SIGNATURES = {
                                 _P, _P, _I32, _U64, _I64, _P, _I32, ctypes.POINTER(ctypes.c_void_p)],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
+    "rcbf_aql_plan_dispatches": [_P],
     "rcbf_aql_plan_free": [_P],
     "rcbf_host_free": [_P],
     "rcbf_version": [],

@@ -9,6 +9,13 @@ dispatch packets are pre-built, and `plan.run()` submits them with one
 doorbell and returns when the K steps have completed -- a synchronous
 env.step() (main.py:93-95, sac_cbf.py:218-238) of K steps.
 
+A plan of K > 1 steps with the exact solver is built in the FUSED form: one
+dispatch in which each lane runs its env's K steps back to back (every step
+still stores everything a step stores), without the fence and the state
+re-load between two dispatches.  `plan.dispatches` tells which form a plan
+took (K: per step; 1 per 4096 steps: fused); `fused=False`, a span buffer,
+`profile=True` or a u_RL buffer that overlaps an output keep the per-step form.
+
 The queue is not a HIP stream: `run()` first waits for all HIP work queued
 on the env's device unless `sync_hip=False` is
 passed by a caller that has synchronised itself (bench.py's timed region
@@ -23,6 +30,7 @@ from . import _lib
 
 PROFILE = 1  # RCBF_AQL_PROFILE
 PROFILE_ENDS = 64  # RCBF_AQL_PROFILE_ENDS: timestamps of the first and last dispatch only
+PER_STEP = 128  # RCBF_AQL_PER_STEP: K dispatches even where the fused form applies
 
 
 def _bind():
@@ -65,11 +73,13 @@ class AqlQueue:
         self._fin()
 
     def safe_step_plan(self, env, u_rl_seq, layer, steps=None, mean=None, sigma=None, outputs=None,
-                       auto_reset=True, prior_layout="rows", span=None, profile=False, fence_flags=0):
+                       auto_reset=True, prior_layout="rows", span=None, profile=False, fence_flags=0, fused=None):
         """K = steps (default len(u_rl_seq)) fused safe steps of `env` with
         `layer`, step j reading u_rl_seq[j % len(u_rl_seq)]: the same
         arguments and results as env.safe_step_seq (span: the measurement
-        instantiation of env.safe_step_span, step j stamping span[j])."""
+        instantiation of env.safe_step_span, step j stamping span[j]).
+        fused: None or True leave the plan's form to the library (fused where
+        it applies, see the module docstring); False asks for K dispatches."""
         if env.device != self.device:
             raise ValueError(f"env on {env.device}, queue on {self.device}")
         o = outputs if outputs is not None else env.make_outputs()
@@ -100,7 +110,8 @@ class AqlQueue:
                 self.handle, ctypes.byref(layer._prm), env.num_envs, K, *[v or None for v in a[2:6]], arr, len(us),
                 None if mean is None else mean.data_ptr(), None if sigma is None else sigma.data_ptr(), int(cols),
                 *[v or None for v in a[9:17]], *a[17:20], None if span is None else span.data_ptr(),
-                (PROFILE if profile else 0) | int(fence_flags), ctypes.byref(h)), "rcbf_aql_safe_step_plan")
+                (PROFILE if profile else 0) | (PER_STEP if fused is False else 0) | int(fence_flags),
+                ctypes.byref(h)), "rcbf_aql_safe_step_plan")
         # the plan holds raw pointers: keep every tensor it reads or writes alive with it
         keep = (env, layer, o, us, mean, sigma, span)
         plan = AqlPlan(self, h, K, keep, bool(profile), env)
@@ -109,7 +120,7 @@ class AqlQueue:
 
 
 class AqlPlan:
-    """K pre-built dispatches of the fused step (see AqlQueue.safe_step_plan)."""
+    """K pre-built steps of the fused step (see AqlQueue.safe_step_plan)."""
 
     def __init__(self, queue, handle, K, keep, profiled, env):
         self.queue, self.K, self.profiled = queue, K, profiled
@@ -126,9 +137,18 @@ class AqlPlan:
         _check(_lib.load().rcbf_aql_run(self._h, timeout_us), "rcbf_aql_run")
         return self._env.obs, self._keep[2]["reward"], self._keep[2]["done"], self._keep[2]
 
+    @property
+    def dispatches(self):
+        """Dispatch packets per run: K in the per-step form, one per 4096 steps in the fused form."""
+        if not self._fin.alive:
+            raise RuntimeError("the AQL plan was freed")
+        return int(_lib.load().rcbf_aql_plan_dispatches(self._h))  # the handle is live: a count, never an error
+
     def times_ns(self):
         """(K, 2) int64 numpy array: each dispatch's start and end (ns, HSA
-        system clock) from the last run; profiled plans only."""
+        system clock) from the last run; profiled plans only.  PROFILE_ENDS:
+        the first dispatch's times in row 0, the last one's in row K - 1 (the
+        same dispatch when the plan has one), 0 between."""
         import numpy as np
         if not self._fin.alive or not self.queue._fin.alive:
             raise RuntimeError("the AQL plan (or its queue) was freed")
