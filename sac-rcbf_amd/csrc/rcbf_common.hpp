@@ -86,6 +86,23 @@ __device__ __forceinline__ void st_out(T* p, T v) {
     __builtin_nontemporal_store(v, p);
 }
 
+// A pointer whose TYPE says global memory.  An access through a plain (generic) pointer is a global_*
+// instruction only where the compiler can trace the pointer back to a kernel argument; through a value it
+// cannot see the origin of (k_safe_steps keeps its pointers behind opaque register copies, and reads its
+// action buffers' addresses from a table in memory) it is a FLAT instruction, which counts in vmcnt AND
+// lgkmcnt and can only be waited for with a full (0).  Through a gptr it is global_* whatever the pointer's
+// history.  The helpers below have a gptr overload each (same flavour, same width).
+template <typename T>
+using gptr = T __attribute__((address_space(1)))*;
+// T* or gptr<T>: the parameter types of code shared by both kinds of caller (safe_step_body)
+template <bool G, typename T>
+using ptr_g = typename std::conditional<G, gptr<T>, T*>::type;
+
+template <typename T>
+__device__ __forceinline__ void st_out(gptr<T> p, T v) {
+    __builtin_nontemporal_store(v, p);
+}
+
 // 16-byte store (staged observation chunks).  WT: write-through (`sc1`), the
 // line leaves the XCD's L2 as it is written instead of waiting, dirty, for the
 // kernel-end write-back.  The cars step takes it (4.40 -> 4.18 us per step,
@@ -102,6 +119,16 @@ __device__ __forceinline__ void st_out4(float* p, float4 v) {
         __builtin_nontemporal_store(w, reinterpret_cast<f4*>(p));
     }
 }
+template <bool WT = false>
+__device__ __forceinline__ void st_out4(gptr<float> p, float4 v) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 w = {v.x, v.y, v.z, v.w};
+    if constexpr (WT) {
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(w) : "memory");
+    } else {
+        __builtin_nontemporal_store(w, reinterpret_cast<gptr<f4>>(p));
+    }
+}
 
 // 16-byte f64 pair store (env state pairs)
 __device__ __forceinline__ void st_out2d(double* p, double a, double b) {
@@ -109,9 +136,18 @@ __device__ __forceinline__ void st_out2d(double* p, double a, double b) {
     d2 w = {a, b};
     __builtin_nontemporal_store(w, reinterpret_cast<d2*>(p));
 }
+__device__ __forceinline__ void st_out2d(gptr<double> p, double a, double b) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 w = {a, b};
+    __builtin_nontemporal_store(w, reinterpret_cast<gptr<d2>>(p));
+}
 
 template <typename T>
 __device__ __forceinline__ T ld_in(const T* p) {
+    return __builtin_nontemporal_load(p);
+}
+template <typename T>
+__device__ __forceinline__ T ld_in(gptr<const T> p) {
     return __builtin_nontemporal_load(p);
 }
 
@@ -130,6 +166,15 @@ __device__ __forceinline__ void st_out2(float* p, float a, float b) {
     w.f[0] = a;
     w.f[1] = b;
     st_out<uint64_t>(reinterpret_cast<uint64_t*>(p), w.u);
+}
+__device__ __forceinline__ void st_out2(gptr<float> p, float a, float b) {
+    union {
+        float f[2];
+        uint64_t u;
+    } w;
+    w.f[0] = a;
+    w.f[1] = b;
+    st_out<uint64_t>(reinterpret_cast<gptr<uint64_t>>(p), w.u);
 }
 
 // ---------------------------------------------------------------------------
@@ -185,6 +230,17 @@ __device__ __forceinline__ void st_any2d(double* p, double a, double b) {
         st_wt2d(p, a, b);
     else
         st_out2d(p, a, b);
+}
+// the gptr forms: `nt` only (the write-through study build keeps generic pointers)
+template <bool WT, typename T>
+__device__ __forceinline__ void st_any(gptr<T> p, T v) {
+    static_assert(!WT, "st_any(gptr): nt only");
+    st_out(p, v);
+}
+template <bool WT>
+__device__ __forceinline__ void st_any2d(gptr<double> p, double a, double b) {
+    static_assert(!WT, "st_any2d(gptr): nt only");
+    st_out2d(p, a, b);
 }
 
 // Staged write-through of a full wave's per-env scalars.  Segment s holds one
@@ -464,6 +520,11 @@ __device__ __forceinline__ void report(int status, int32_t* status_out, int64_t 
     if (status_out) status_out[i] = status;
     if (status != RCBF_QP_OK && fail_flag) atomicOr(fail_flag, 1 << status);
 }
+__device__ __forceinline__ void report(int status, gptr<int32_t> status_out, int64_t i, gptr<int32_t> fail_flag) {
+    if (status_out) status_out[i] = status;
+    if (status != RCBF_QP_OK && fail_flag)  // atomicOr's own builtin, on the typed pointer
+        __hip_atomic_fetch_or(fail_flag, 1 << status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // ---------------------------------------------------------------------------
 // environments
@@ -530,9 +591,9 @@ __device__ __forceinline__ void state_from_env(const double* xs, float* s32) {
 // The episode counter is only touched when the env resets.
 // obs_cache (unicycle): cos/sin/goal distance of the post-step state, valid
 // unless the env was reset (then obs_cache[3] = 0 and the obs is recomputed).
-template <int SOLVER, int MODE, int K, bool ST = false, bool WT = false>
+template <int SOLVER, int MODE, int K, bool ST = false, bool WT = false, typename EP = uint32_t*>
 __device__ __forceinline__ void safe_step_one(const rcbf_params& prm, int64_t i, double* xs, double& a, int& st,
-                                              uint32_t* episode, const float* us, const float* m, const float* s,
+                                              EP episode, const float* us, const float* m, const float* s,
                                               float* uf, float& rew, float& cst, bool& dn, bool& gm, int& status,
                                               int auto_reset, uint64_t seed, int64_t off,
                                               const Stamps<ST>& stamps = {}, double* obs_cache = nullptr,

@@ -58,16 +58,17 @@ __device__ __forceinline__ void load_state(const double* x, int64_t B, int64_t i
     if constexpr (NS % 2) xs[NS - 1] = ld_in(&x[(NS - 1) * B + i]);
 }
 
-template <int MODE>
-__device__ __forceinline__ void store_state(double* x, int64_t B, int64_t i, const double* xs) {
+template <int MODE, typename XP = double*>  // XP: double* or gptr<double>
+__device__ __forceinline__ void store_state(XP x, int64_t B, int64_t i, const double* xs) {
     constexpr int NS = Dims<MODE, 1>::NS;
 #pragma unroll
     for (int p = 0; p < NS / 2; ++p) st_out2d(&x[2 * (p * B + i)], xs[2 * p], xs[2 * p + 1]);
     if constexpr (NS % 2) st_out(&x[(NS - 1) * B + i], xs[NS - 1]);
 }
 
-template <int MODE, bool WT = false>
-__device__ __forceinline__ void store_obs32(float* obs, int64_t i, const double* xs,
+// OP (here and below): float* or gptr<float>
+template <int MODE, bool WT = false, typename OP = float*>
+__device__ __forceinline__ void store_obs32(OP obs, int64_t i, const double* xs,
                                             const double* obs_cache = nullptr) {
     constexpr int NO = Dims<MODE, 1>::NO;
     double o[NO];
@@ -80,7 +81,7 @@ __device__ __forceinline__ void store_obs32(float* obs, int64_t i, const double*
         env_obs<MODE>(xs, o);
     }
     if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) {
-        float* ov = obs + i * NO;  // 40 B rows, 8 B aligned
+        const OP ov = obs + i * NO;  // 40 B rows, 8 B aligned
 #pragma unroll
         for (int k = 0; k < NO / 2; ++k) {
             if constexpr (WT) {
@@ -102,14 +103,14 @@ __device__ __forceinline__ void store_obs32(float* obs, int64_t i, const double*
 // chunks, chunk c by lane c % 64.  Every chunk is read from LDS first, then
 // stored: the write-through store is an asm with a memory clobber, which
 // would otherwise hold each following LDS read (and its wait) behind the
-// previous store.
-template <int MODE, bool WT = false>
-__device__ __forceinline__ void store_obs_chunks(float* obs, int64_t base, const float* lds_wave, int lane) {
+// previous store.  SC1: the chunks leave write-through (st_out4).
+template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*>
+__device__ __forceinline__ void store_obs_chunks(OP obs, int64_t base, const float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
     __builtin_amdgcn_wave_barrier();
     constexpr int CH = NO * 16;  // 16-byte chunks in the wave's block
     const float4* src = reinterpret_cast<const float4*>(lds_wave);
-    float* dst = obs + base * NO;
+    const OP dst = obs + base * NO;
     constexpr int NJ = (CH + 63) / 64;
     float4 chunk[NJ];
 #pragma unroll
@@ -120,7 +121,7 @@ __device__ __forceinline__ void store_obs_chunks(float* obs, int64_t base, const
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int c = j * 64 + lane;
-        if (CH % 64 == 0 || c < CH) st_out4<WT || MODE == RCBF_MODE_SIMULATED_CARS>(dst + 4 * c, chunk[j]);
+        if (CH % 64 == 0 || c < CH) st_out4<SC1>(dst + 4 * c, chunk[j]);
     }
 }
 
@@ -129,8 +130,8 @@ __device__ __forceinline__ void store_obs_chunks(float* obs, int64_t base, const
 // store the block as 16-byte chunks, chunk c by lane c%64 -- every store
 // instruction covers whole contiguous lines (cars: 3 dwordx4 instead of 5
 // strided dwordx2).  Partial or unaligned waves take the per-lane path.
-template <int MODE, bool WT = false>
-__device__ __forceinline__ void store_obs32_staged(float* obs, int64_t i, int64_t B, const double* xs,
+template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*>
+__device__ __forceinline__ void store_obs32_staged(OP obs, int64_t i, int64_t B, const double* xs,
                                                    const double* obs_cache, float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
     const int64_t base = i - lane;
@@ -160,7 +161,7 @@ __device__ __forceinline__ void store_obs32_staged(float* obs, int64_t i, int64_
 #pragma unroll
         for (int k = 0; k < NO; ++k) lds_wave[lane * NO + k] = (float)o[k];
     }
-    store_obs_chunks<MODE, WT>(obs, base, lds_wave, lane);
+    store_obs_chunks<MODE, WT, SC1>(obs, base, lds_wave, lane);
 }
 
 // One fused safe step of env i, from its state and inputs in registers (xs, a,
@@ -168,18 +169,24 @@ __device__ __forceinline__ void store_obs32_staged(float* obs, int64_t i, int64_
 // reset_foreseeable) to every store a step makes: the state pairs, aux, step,
 // the episode counter on a reset, the observation (staged through obs_stage,
 // this wave's 64 x NO floats of LDS; lane: threadIdx.x & 63), u, reward, cost, done, goal_met, the
-// status and the fail_flag OR.  xs, a and st come back as the post-step state.
+// status and the fail_flag OR.  xs, a and st come back as the post-step state,
+// *did_reset (if asked for) whether the step reset the env.
 // Shared by k_safe_step (one step per dispatch) and k_safe_steps (K steps per
 // dispatch): one source for both.  wt_lds: the write-through staging block of
-// the RCBF_WT_OUT study build.
-template <int SOLVER, int MODE, int K, bool ST, bool WT>
+// the RCBF_WT_OUT study build.  GP: the buffers come as gptr (k_safe_steps), so every access is a global_*
+// instruction by type; k_safe_step passes its kernel arguments as they are.  OBS_SC1: the staged observation
+// chunks' store flavour (st_out4).
+template <int SOLVER, int MODE, int K, bool ST, bool WT, bool GP = false,
+          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS>
 __device__ __forceinline__ void safe_step_body(
-    const rcbf_params& prm, int64_t B, int64_t i, double* __restrict__ x, double* __restrict__ aux,
-    int32_t* __restrict__ step, uint32_t* __restrict__ episode, float* __restrict__ obs_out,
-    float* __restrict__ u_out, float* __restrict__ reward, float* __restrict__ cost, uint8_t* __restrict__ done,
-    uint8_t* __restrict__ goal_met, int32_t* __restrict__ status_out, int32_t* fail_flag, int auto_reset,
+    const rcbf_params& prm, int64_t B, int64_t i, ptr_g<GP, double> __restrict__ x, ptr_g<GP, double> __restrict__ aux,
+    ptr_g<GP, int32_t> __restrict__ step, ptr_g<GP, uint32_t> __restrict__ episode,
+    ptr_g<GP, float> __restrict__ obs_out, ptr_g<GP, float> __restrict__ u_out, ptr_g<GP, float> __restrict__ reward,
+    ptr_g<GP, float> __restrict__ cost, ptr_g<GP, uint8_t> __restrict__ done, ptr_g<GP, uint8_t> __restrict__ goal_met,
+    ptr_g<GP, int32_t> __restrict__ status_out, ptr_g<GP, int32_t> fail_flag, int auto_reset,
     uint64_t seed, int64_t off, double* xs, double& a, int& st, const float* us, const float* m, const float* s,
-    bool ep_pre, uint32_t ep0, const Stamps<ST>& stamps, float* obs_stage, char* wt_lds, int lane) {
+    bool ep_pre, uint32_t ep0, const Stamps<ST>& stamps, float* obs_stage, char* wt_lds, int lane,
+    bool* did_reset = nullptr) {
     using D = Dims<MODE, K>;
     const int64_t wbase = i - lane;
     const bool wfull = wbase + 64 <= B;  // wave-uniform: every lane of this wave is live
@@ -261,7 +268,7 @@ __device__ __forceinline__ void safe_step_body(
             st_out(&step[i], st);
         }
     }
-    store_obs32_staged<MODE, WT>(obs_out, i, B, xs, oc, obs_stage, lane);
+    store_obs32_staged<MODE, WT, OBS_SC1>(obs_out, i, B, xs, oc, obs_stage, lane);
     if constexpr (WT) {
         constexpr int NU4 = 4 * D::NU;
         float ufc[D::NU];
@@ -313,6 +320,7 @@ __device__ __forceinline__ void safe_step_body(
         st_out(&done[i], (uint8_t)dn);
         if (goal_met) st_out(&goal_met[i], (uint8_t)gm);
     }
+    if (did_reset) *did_reset = auto_reset && dn;  // the condition under which the step above reset the env
     stamps.mark(6, false);
     if constexpr (WT) {
         if (status_out) st_wt(&status_out[i], (int32_t)status);
@@ -431,6 +439,16 @@ __global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict_
     }
 }
 
+// k_safe_steps: which kernels keep their loop's values in plain variables (true) and which behind opaque
+// copies in accumulation registers (false; see the kernel): plain wherever the kernel then has no scalar or
+// vector spill and no scratch (tests/test_abi_fused_cpu.py).  Cars fits (168 VGPRs, 106 SGPRs) and so does
+// the unicycle at k = 1; written plain, the unicycle at k = 2, 3, 4, 5, 6 spills 2, 6, 8, 12, 8 scalar
+// registers (256-thread workgroups).
+template <int MODE, int K>
+constexpr bool fused_plain() {
+    return MODE == RCBF_MODE_SIMULATED_CARS || K == 1;
+}
+
 // Argument block of k_safe_steps, at the offsets of its parameter list (the
 // AMDGPU kernarg ABI: every argument at its natural alignment): k_safe_step's
 // block with the u_RL table in u_rl's place and n_u, steps, ju0 in the stamp
@@ -497,19 +515,34 @@ __global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict
     using D = Dims<MODE, K>;
     constexpr int SOLVER = RCBF_SOLVER_ACTIVE_SET;
     constexpr bool WT = false;
+    constexpr bool PLAIN = fused_plain<MODE, K>();
+    // the staged observation chunks leave `nt` here, cars included: no kernel end follows a step, the next
+    // step rewrites the line, and `sc1` would write each step's chunks through to HBM (measured: DESIGN 5.2)
+    constexpr bool OBS_SC1 = false;
     int64_t i = env_index<BS>();
     if (i >= B) return;
     double xs[D::NS];
     load_state<MODE>(x, B, i, xs);
     double a = ld_in(&aux[i]);
     int st = ld_in(&step[i]);
-    int ju = ju0;
+    // The u_RL table, read with scalar loads: its address, ju0, n_u and steps are the same for every lane,
+    // and nothing writes it while a plan runs, which its type says (the constant address space: a uniform
+    // load from it is a scalar load wherever it stands among the loop's stores).  Its entries are addresses
+    // of global memory, and are typed so (gptr, rcbf_common.hpp).
+    typedef const uint64_t __attribute__((address_space(4)))* ctab_t;
+    const ctab_t tab = (ctab_t)reinterpret_cast<const uint64_t*>(u_tab);
     float us[D::NU], m[D::NS], s[D::NS];
     {
-        const float* __restrict__ u0 = u_tab[ju];
+        const gptr<const float> u0 = reinterpret_cast<gptr<const float>>(tab[ju0]);
 #pragma unroll
         for (int c = 0; c < D::NU; ++c) us[c] = ld_in(&u0[i * D::NU + c]);
     }
+    // env i's episode counter, which only this lane writes (at a reset): read once, then kept in a register
+    uint32_t epr = episode ? ld_in(&episode[i]) : 0u;
+    // step 1's buffer: every step issues the load of the next step's action from an address that the step
+    // before it fetched, so neither the table entry nor the action is ever waited for where it is asked for
+    int ju = ju0 + 1 == n_u ? 0 : ju0 + 1;
+    gptr<const float> u_next = reinterpret_cast<gptr<const float>>(tab[ju]);
     if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) prefetch_kernargs<7>();
     // the priors: inputs of the plan that nothing in a run writes, loaded once (k_safe_step's layouts)
     if (prior_cols) {
@@ -539,82 +572,124 @@ __global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict
         }
     }
     __shared__ float obs_stage[BS / 64][64 * D::NO];
+    // k = 8 only: the parameter block, one copy per wave, written by every live lane of the wave (the same
+    // values; a wave's LDS operations execute in order, so its reads below see them)
+    __shared__ rcbf_params prm_stage[K >= 8 ? BS / 64 : 1];
+    if constexpr (K >= 8) {
+        prm_stage[threadIdx.x >> 6] = prm;
+        __builtin_amdgcn_wave_barrier();
+    }
     const Stamps<false> stamps{};
     // Register budget of the loop.  Whatever the body derives from loop-invariant values alone (null
     // tests and per-lane addresses of the 15 buffers, the 60 dwords of the parameter block, the loop's
     // own counters) the compiler hoists out of the loop, where it stays live over the whole body on top
-    // of what one step needs -- and the unicycle step alone takes every scalar register there is, and
-    // at 7 and 8 hazards every vector register.  So everything the loop carries beside the env's state
-    // lives in accumulation registers (the unified file has room there: 230 of 256 used at k = 8), as
-    // uniform per-lane values behind empty asm copies the compiler cannot see through; no instruction
-    // is emitted for a copy, a use costs one register read.  Every step then derives from them what
-    // k_safe_step derives once per dispatch, and the parameter block is read from the argument segment
-    // again (scalar loads that hit the scalar cache; vector loads at k = 8).  No kernel spills.
+    // of what one step needs.  Where that fits (PLAIN, fused_plain above) the loop is written as it reads.
+    // The unicycle step alone takes every scalar register there is, and at 7 and 8 hazards every vector
+    // register: there everything the loop carries beside the env's state lives in accumulation registers
+    // (the unified file has room), as uniform per-lane values behind empty asm copies the compiler cannot
+    // see through; no instruction is emitted for a copy, a use costs one register read.  Every step then
+    // derives from them what k_safe_step derives once per dispatch, and the parameter block is read from
+    // the argument segment again (scalar loads that hit the scalar cache; vector loads at k = 8).  The
+    // walk of the table stays scalar: the wave-uniform values are read back with readfirstlane.  In both
+    // forms the buffers are gptr, so every access is a global_* instruction.  No kernel spills.
     int64_t Bv = B;
-    double* xv = x;
-    double* auxv = aux;
-    int32_t* stepv = step;
-    uint32_t* epv = episode;
-    float* obsv = obs_out;
-    float* uv = u_out;
-    float* rewv = reward;
-    float* costv = cost;
-    uint8_t* donev = done;
-    uint8_t* goalv = goal_met;
-    int32_t* statv = status_out;
-    int32_t* failv = fail_flag;
-    const float* const* tabv = u_tab;
+    gptr<double> xv = (gptr<double>)x;
+    gptr<double> auxv = (gptr<double>)aux;
+    gptr<int32_t> stepv = (gptr<int32_t>)step;
+    gptr<uint32_t> epv = (gptr<uint32_t>)episode;
+    gptr<float> obsv = (gptr<float>)obs_out;
+    gptr<float> uv = (gptr<float>)u_out;
+    gptr<float> rewv = (gptr<float>)reward;
+    gptr<float> costv = (gptr<float>)cost;
+    gptr<uint8_t> donev = (gptr<uint8_t>)done;
+    gptr<uint8_t> goalv = (gptr<uint8_t>)goal_met;
+    gptr<int32_t> statv = (gptr<int32_t>)status_out;
+    gptr<int32_t> failv = (gptr<int32_t>)fail_flag;
+    uint64_t tabv = reinterpret_cast<uint64_t>(u_tab), unextv = reinterpret_cast<uint64_t>(u_next);
     int arv = auto_reset, lanev = threadIdx.x & 63, nuv = n_u, juv = ju, leftv = steps,
         widv = threadIdx.x >> 6;
     uint64_t seedv = seed;
     int64_t offv = off;
-#define RCBF_OPAQUE_V()                                                                                         \
-    asm volatile("" : "+a"(xv), "+a"(auxv), "+a"(stepv), "+a"(epv), "+a"(obsv), "+a"(uv), "+a"(rewv));        \
-    asm volatile("" : "+a"(costv), "+a"(donev), "+a"(goalv), "+a"(statv), "+a"(failv), "+a"(tabv), "+a"(Bv), \
-                 "+a"(arv), "+a"(lanev), "+a"(i));                                                              \
-    asm volatile("" : "+a"(widv), "+a"(nuv), "+a"(juv), "+a"(leftv), "+a"(seedv), "+a"(offv))
+#define RCBF_OPAQUE_V()                                                                                          \
+    if constexpr (!PLAIN) {                                                                                      \
+        asm volatile("" : "+a"(xv), "+a"(auxv), "+a"(stepv), "+a"(epv), "+a"(obsv), "+a"(uv), "+a"(rewv));     \
+        asm volatile("" : "+a"(costv), "+a"(donev), "+a"(goalv), "+a"(statv), "+a"(failv), "+a"(epr),         \
+                     "+a"(Bv), "+a"(arv), "+a"(lanev), "+a"(i));                                                 \
+        asm volatile("" : "+a"(widv), "+a"(tabv), "+a"(nuv), "+a"(juv), "+a"(leftv), "+a"(seedv), "+a"(offv),   \
+                     "+a"(unextv));                                                                              \
+    }
     RCBF_OPAQUE_V();  // once: uniform values, kept in accumulation registers from here on
+    // Everything loaded so far has arrived before the loop is entered (vmcnt(0); expcnt and lgkmcnt left
+    // alone).  A wait for one of these loads inside the loop would be passed again in every step, where all
+    // it can wait for is the last step's stores.
+    __builtin_amdgcn_s_waitcnt(0x0f70);
 #pragma nounroll
     while (leftv > 0) {
         RCBF_OPAQUE_V();  // every step: nothing derived from them is loop-invariant to the compiler
-#pragma unroll
-        for (int k = 0; k < D::NS; ++k) asm volatile("" : "+a"(m[k]), "+a"(s[k]));  // the priors too
         const rcbf_params* prm_p = &prm;
-        if constexpr (K >= 8) {
-            // k = 8: the step's scalar registers are all taken, so its parameters come through vector loads
-            // (the block's address in the argument segment, as a per-lane value)
-            prm_p = reinterpret_cast<const rcbf_params*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                         offsetof(SafeStepsArgs, prm));
-            asm volatile("" : "+v"(prm_p));
-        } else {
-            uint32_t prm_off = 0;
-            asm volatile("" : "+s"(prm_off));
-            prm_p = reinterpret_cast<const rcbf_params*>(reinterpret_cast<const char*>(&prm) + prm_off);
+        if constexpr (!PLAIN) {
+#pragma unroll
+            for (int k = 0; k < D::NS; ++k) asm volatile("" : "+a"(m[k]), "+a"(s[k]));  // the priors too
+            if constexpr (K >= 8) {
+                // k = 8: the step's scalar registers are all taken, so its parameters are read per lane, from
+                // this wave's copy in LDS (prm_stage; behind a per-lane zero the compiler cannot see through,
+                // which keeps the LDS provenance: ds_read).  Vector loads from the argument segment would count
+                // in vmcnt behind the last step's stores, and waiting for them would wait for those.
+                uint32_t prm_voff = 0;
+                asm volatile("" : "+v"(prm_voff));
+                prm_p = reinterpret_cast<const rcbf_params*>(reinterpret_cast<const char*>(&prm_stage[widv]) +
+                                                             prm_voff);
+            } else {
+                uint32_t prm_off = 0;
+                asm volatile("" : "+s"(prm_off));
+                prm_p = reinterpret_cast<const rcbf_params*>(reinterpret_cast<const char*>(&prm) + prm_off);
+            }
         }
         const rcbf_params& prm_j = *prm_p;
-        // the next step's action, issued ahead of this step's chain
+        // the next step's action, issued ahead of this step's chain from the address the last step fetched
         float un[D::NU];
 #pragma unroll
         for (int c = 0; c < D::NU; ++c) un[c] = 0.0f;
         --leftv;
         if (leftv > 0) {
-            juv = juv + 1 == nuv ? 0 : juv + 1;
-            const float* __restrict__ u1 = tabv[juv];
+            const gptr<const float> u1 = reinterpret_cast<gptr<const float>>(unextv);
 #pragma unroll
             for (int c = 0; c < D::NU; ++c) un[c] = ld_in(&u1[i * D::NU + c]);
         }
-        // the counter this lane itself stored at its last reset, re-read only when a reset is foreseeable
-        const bool ep_pre = epv && reset_foreseeable<MODE>(st, a);
-        uint32_t ep0 = 0;
-        if (ep_pre) ep0 = epv[i];
-        safe_step_body<SOLVER, MODE, K, false, WT>(prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv, costv, donev,
-                                                   goalv, statv, failv, arv, seedv, offv, xs, a, st, us, m, s,
-                                                   ep_pre, ep0, stamps, obs_stage[widv], nullptr, lanev);
+        // the address of the buffer of the step after the next: a scalar load (an entry of the table whether
+        // or not that step runs), whose result is first needed at the end of this step
+        uint64_t unext2;
+        {
+            int nu_s = n_u, ju_s = juv;
+            uint64_t tab_s = reinterpret_cast<uint64_t>(u_tab);
+            if constexpr (!PLAIN) {
+                // out of their accumulation registers, as the wave-uniform values they are
+                tab_s = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(tabv >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tabv);
+                nu_s = __builtin_amdgcn_readfirstlane(nuv);
+                ju_s = __builtin_amdgcn_readfirstlane(juv);
+            }
+            ju_s = ju_s + 1 == nu_s ? 0 : ju_s + 1;
+            juv = ju_s;
+            unext2 = reinterpret_cast<ctab_t>(tab_s)[ju_s];
+        }
+        bool rs = false;
+        safe_step_body<SOLVER, MODE, K, false, WT, true, OBS_SC1>(prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv,
+                                                                  costv, donev, goalv, statv, failv, arv, seedv, offv,
+                                                                  xs, a, st, us, m, s, epv != nullptr, epr, stamps,
+                                                                  obs_stage[widv], nullptr, lanev, &rs);
+        epr += rs ? 1u : 0u;  // a reset stored epr + 1
         // this step's chunk reads of obs_stage stay ahead of the next step's writes to it (one wave's LDS
         // operations execute in order; this keeps the compiler from reordering them)
         __builtin_amdgcn_wave_barrier();
+        // every step's stores are made in that step: without this the compiler, which sees in the plain form
+        // that a step overwrites what the last one stored to aux, step, u, reward, cost and done, keeps those
+        // in registers and stores them once after the loop (no instruction, no wait: a compiler barrier)
+        asm volatile("" ::: "memory");
 #pragma unroll
         for (int c = 0; c < D::NU; ++c) us[c] = un[c];
+        if constexpr (!PLAIN) asm volatile("" : "+s"(unext2));  // a scalar load's result, scalar till here
+        unextv = unext2;
     }
 #undef RCBF_OPAQUE_V
 }
