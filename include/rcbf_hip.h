@@ -558,7 +558,48 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
  * doorbell once, busy-wait for completion; timeout_us 0 -> 10 s.  A plan
  * must not run after rcbf_aql_close of its queue (rcbf_aql_plan_free may
  * still be called then).
- * Returns RCBF_E_HSA / RCBF_E_TIMEOUT on a queue error or a timeout. */
+ * Returns RCBF_E_HSA / RCBF_E_TIMEOUT on a queue error or a timeout.
+ *
+ * rcbf_aql_safe_step_traj_plan: a plan that keeps EVERY step's outputs, for
+ * stepping with pre-known actions where each step's observation, action,
+ * reward, cost and done are wanted: the warm-up phase (main.py:88-107, random
+ * actions pushed to the replay memory step by step) and evaluation rollouts.
+ * The arguments of rcbf_aql_safe_step_plan, then traj_mask (RCBF_TRAJ_* bits:
+ * which outputs to record) and traj_pitch = P, the row pitch in envs.
+ *   - The pointer passed for a recorded output is the base of a dense
+ *     (K, P, w) array, w the output's per-env width (n_o for obs, n_u for u,
+ *     else 1).  Step j of the plan writes env i's value at [j][i]: exactly
+ *     what the j-th of K single-step launches leaves in its (B, w) buffer --
+ *     on a step that auto-resets, obs[j] is the reset observation (the next
+ *     episode's first), as rcbf_safe_step stores it.  Columns [B, P) and rows
+ *     >= K are never written.
+ *   - An output whose bit is clear is overwritten in place every step, as in
+ *     a plain plan.  x, aux, step, episode and fail_flag are never
+ *     trajectories: after the run they hold what K launches leave.
+ *   - P >= B and P % 4 == 0, and a recorded obs base is 16-byte aligned:
+ *     otherwise RCBF_E_BAD_SHAPE (every row then starts on a 16-byte
+ *     boundary, which the observation's 16-byte chunk stores need).
+ *   - The bit of a NULL pointer (goal_met, status_out) is cleared: nothing is
+ *     written through it and it is never advanced.
+ *   - span_out with a non-zero mask: RCBF_E_BAD_MODE.
+ *   - Running the plan again writes rows 0 .. K - 1 again, from the state the
+ *     previous run left.
+ *   - traj_mask == 0: the plan rcbf_aql_safe_step_plan builds; traj_pitch is
+ *     ignored.
+ * Forms: FUSED under rcbf_aql_safe_step_plan's conditions (one dispatch of
+ * k_safe_steps_traj per chunk of at most 4096 steps, which moves each
+ * recorded pointer one row on after every step; the u_RL overlap check covers
+ * the whole (K, P, w) extent of every recorded output); otherwise PER STEP: K
+ * dispatches of k_safe_step, step j's argument block pointing each recorded
+ * output at row j.  The queries, rcbf_aql_run and rcbf_aql_plan_free work on
+ * these plans unchanged. */
+#define RCBF_TRAJ_OBS 1
+#define RCBF_TRAJ_U 2
+#define RCBF_TRAJ_REWARD 4
+#define RCBF_TRAJ_COST 8
+#define RCBF_TRAJ_DONE 16
+#define RCBF_TRAJ_GOAL_MET 32
+#define RCBF_TRAJ_STATUS 64
 #define RCBF_AQL_PROFILE 1
 /* plan flags: memory-fence scopes (default: agent scope everywhere but the
  * last packet's release, which is system scope) */
@@ -571,6 +612,7 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
 #define RCBF_AQL_PER_STEP 128           /* build the per-step form (K dispatches) even where the fused form applies */
 #define RCBF_AQL_SAFE_STEP_KERNARG_BYTES 408 /* sizeof the k_safe_step argument block */
 #define RCBF_AQL_SAFE_STEPS_KERNARG_BYTES 408 /* sizeof the k_safe_steps (fused form) argument block */
+#define RCBF_AQL_SAFE_STEPS_TRAJ_KERNARG_BYTES 424 /* ... of k_safe_steps_traj: + traj_mask (408), traj_pitch (416) */
 typedef struct rcbf_aql rcbf_aql;
 typedef struct rcbf_aql_plan rcbf_aql_plan;
 int rcbf_aql_open(int32_t device, const char* code_object, int32_t flags, rcbf_aql** out);
@@ -582,6 +624,13 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
                             float* reward, float* cost, uint8_t* done, uint8_t* goal_met, int32_t* status_out,
                             int32_t* fail_flag, int32_t auto_reset, uint64_t seed, int64_t env_offset,
                             uint64_t* span_out, int32_t flags, rcbf_aql_plan** out);
+int rcbf_aql_safe_step_traj_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                                 int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
+                                 const float* mu, const float* sigma, int32_t prior_cols, float* obs_out,
+                                 float* u_out, float* reward, float* cost, uint8_t* done, uint8_t* goal_met,
+                                 int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
+                                 int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
+                                 int64_t traj_pitch, rcbf_aql_plan** out);
 int rcbf_aql_run(rcbf_aql_plan* plan, uint64_t timeout_us);
 int rcbf_aql_plan_times(const rcbf_aql_plan* plan, uint64_t* start_end_ns);
 int rcbf_aql_plan_dispatches(const rcbf_aql_plan* plan);

@@ -103,6 +103,8 @@ static_assert(offsetof(SafeStepArgs, stamp_buf) == 400, "kernarg layout");
 static_assert(sizeof(SafeStepArgs) == RCBF_AQL_SAFE_STEP_KERNARG_BYTES, "kernarg layout");
 // the fused form's kernel (rcbf::k_safe_steps) takes rcbf::SafeStepsArgs, defined next to it
 static_assert(sizeof(SafeStepsArgs) == RCBF_AQL_SAFE_STEPS_KERNARG_BYTES, "kernarg layout");
+// ... and its trajectory form (rcbf::k_safe_steps_traj) rcbf::SafeStepsTrajArgs
+static_assert(sizeof(SafeStepsTrajArgs) == RCBF_AQL_SAFE_STEPS_TRAJ_KERNARG_BYTES, "kernarg layout");
 
 struct KernelInfo {
     std::string name;  // mangled symbol without ".kd"
@@ -111,7 +113,10 @@ struct KernelInfo {
 };
 
 constexpr uint32_t kQueueSize = 4096;  // packets (power of two); a plan longer than this is fed in chunks
-constexpr size_t kArgStride = 512;     // bytes per step's kernarg block (>= 408, 64-B multiple)
+constexpr size_t kArgStride = 512;     // bytes per step's kernarg block (>= 424, 64-B multiple)
+static_assert(sizeof(SafeStepsTrajArgs) <= kArgStride, "kernarg block");
+constexpr int32_t kTrajAll = RCBF_TRAJ_OBS | RCBF_TRAJ_U | RCBF_TRAJ_REWARD | RCBF_TRAJ_COST | RCBF_TRAJ_DONE |
+                             RCBF_TRAJ_GOAL_MET | RCBF_TRAJ_STATUS;
 constexpr int32_t kFusedChunk = (int32_t)kQueueSize;  // most steps one fused dispatch runs: a bounded kernel
 
 uint64_t now_ns() {
@@ -127,13 +132,16 @@ struct rcbf_aql {
     hsa_agent_t agent{};
     hsa_queue_t* queue = nullptr;
     hsa_code_object_reader_t reader{};
+    hsa_code_object_reader_t reader_traj{};  // librcbf_steps_traj.co (the k_safe_steps_traj kernels), if there
     hsa_executable_t exe{};
-    bool have_reader = false, have_exe = false, hsa_up = false;
-    std::vector<char> code;
+    hsa_executable_t exe_traj{};  // its own executable: no symbol of one code object can meet one of the other
+    bool have_reader = false, have_reader_traj = false, have_exe = false, have_exe_traj = false, hsa_up = false;
+    std::vector<char> code, code_traj;
     std::vector<KernelInfo> kernels;
     std::atomic<int> queue_error{0};
     int profiling = 0;
     bool fused = false;  // the code object has the k_safe_steps kernels (the fused plan form)
+    bool traj = false;   // ... and the k_safe_steps_traj kernels (the fused form of a trajectory plan)
 };
 
 struct rcbf_aql_plan {
@@ -217,6 +225,19 @@ std::string safe_steps_prefix(int mode, int k, int bs) {
     return buf;
 }
 
+// ... and of rcbf::k_safe_steps_traj<MODE, K, BS> (SafeStepsTrajArgs)
+std::string safe_steps_traj_prefix(int mode, int k, int bs) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "_ZN4rcbf17k_safe_steps_trajILi%dELi%dELi%dEEEv", mode, k, bs);
+    return buf;
+}
+
+// p moved on by `rows` rows of `row_bytes` bytes (64-bit arithmetic); a null pointer stays null
+template <typename T>
+T* rows_on(T* p, int64_t rows, int64_t row_bytes) {
+    return p ? reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(p) + rows * row_bytes) : nullptr;
+}
+
 bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
@@ -250,7 +271,9 @@ void destroy(rcbf_aql* q) {
     if (!q) return;
     if (q->queue) hsa_queue_destroy(q->queue);
     if (q->have_exe) hsa_executable_destroy(q->exe);
+    if (q->have_exe_traj) hsa_executable_destroy(q->exe_traj);
     if (q->have_reader) hsa_code_object_reader_destroy(q->reader);
+    if (q->have_reader_traj) hsa_code_object_reader_destroy(q->reader_traj);
     if (q->hsa_up) hsa_shut_down();
     delete q;
 }
@@ -289,6 +312,23 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
         delete q;
         return RCBF_E_BAD_SHAPE;
     }
+    // the trajectory plans' kernels: NAME_traj.co beside NAME.co.  Without it the queue opens as before and
+    // trajectory plans take the per-step form.
+    if (path.size() > 3 && path.compare(path.size() - 3, 3, ".co") == 0) {
+        const std::string tpath = path.substr(0, path.size() - 3) + "_traj.co";
+        if (FILE* tf = fopen(tpath.c_str(), "rb")) {
+            fseek(tf, 0, SEEK_END);
+            const long tn = ftell(tf);
+            fseek(tf, 0, SEEK_SET);
+            q->code_traj.resize(tn > 0 ? (size_t)tn : 0);
+            const bool ok = tn > 0 && fread(q->code_traj.data(), 1, (size_t)tn, tf) == (size_t)tn;
+            fclose(tf);
+            if (!ok) {  // there, but unreadable: an error, not a quiet fall back
+                delete q;
+                return RCBF_E_BAD_SHAPE;
+            }
+        }
+    }
     int rc = hsa_rc(hsa_init());
     if (rc) {
         delete q;
@@ -318,11 +358,25 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     if (!rc) rc = hsa_rc(hsa_executable_load_agent_code_object(q->exe, q->agent, q->reader, nullptr, nullptr));
     if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe, nullptr));
     if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe, q->agent, collect_kernel, q));
+    if (!rc && !q->code_traj.empty()) {
+        rc = hsa_rc(
+            hsa_code_object_reader_create_from_memory(q->code_traj.data(), q->code_traj.size(), &q->reader_traj));
+        if (!rc) q->have_reader_traj = true;
+        if (!rc)
+            rc = hsa_rc(hsa_executable_create_alt(HSA_PROFILE_FULL, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr,
+                                                  &q->exe_traj));
+        if (!rc) q->have_exe_traj = true;
+        if (!rc)
+            rc = hsa_rc(
+                hsa_executable_load_agent_code_object(q->exe_traj, q->agent, q->reader_traj, nullptr, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_traj, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_traj, q->agent, collect_kernel, q));
+    }
     // every k_safe_step instantiation in the code object must take exactly the
     // argument block SafeStepArgs describes
     // ... and every k_safe_steps instantiation SafeStepsArgs; a code object without them still opens, and
-    // its plans take the per-step form
-    int n_steps = 0, n_fused = 0;
+    // its plans take the per-step form; likewise k_safe_steps_traj and SafeStepsTrajArgs
+    int n_steps = 0, n_fused = 0, n_traj = 0;
     for (const auto& k : q->kernels) {
         if (k.name.compare(0, 21, "_ZN4rcbf11k_safe_step") == 0) {
             ++n_steps;
@@ -330,10 +384,14 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
         } else if (k.name.compare(0, 22, "_ZN4rcbf12k_safe_steps") == 0) {
             ++n_fused;
             if (k.kernarg_bytes != sizeof(SafeStepsArgs) || k.private_bytes != 0) rc = RCBF_E_BAD_SHAPE;
+        } else if (k.name.compare(0, 27, "_ZN4rcbf17k_safe_steps_traj") == 0) {
+            ++n_traj;
+            if (k.kernarg_bytes != sizeof(SafeStepsTrajArgs) || k.private_bytes != 0) rc = RCBF_E_BAD_SHAPE;
         }
     }
     if (!rc && n_steps == 0) rc = RCBF_E_BAD_MODE;
     q->fused = n_fused > 0;
+    q->traj = n_traj > 0;
     if (!rc)
         rc = hsa_rc(hsa_queue_create(q->agent, kQueueSize, HSA_QUEUE_TYPE_SINGLE, queue_error_cb, q, UINT32_MAX,
                                      UINT32_MAX, &q->queue));
@@ -353,12 +411,14 @@ int rcbf_aql_close(rcbf_aql* q) {
 
 int rcbf_aql_kernel_count(const rcbf_aql* q) { return q ? (int)q->kernels.size() : RCBF_E_NULL; }
 
-int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
-                            int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
-                            const float* mu, const float* sigma, int32_t prior_cols, float* obs_out, float* u_out,
-                            float* reward, float* cost, uint8_t* done, uint8_t* goal_met, int32_t* status_out,
-                            int32_t* fail_flag, int32_t auto_reset, uint64_t seed, int64_t env_offset,
-                            uint64_t* span_out, int32_t flags, rcbf_aql_plan** out) {
+// rcbf_aql_safe_step_plan (traj_mask = 0) and rcbf_aql_safe_step_traj_plan
+static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                                int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
+                                const float* mu, const float* sigma, int32_t prior_cols, float* obs_out,
+                                float* u_out, float* reward, float* cost, uint8_t* done, uint8_t* goal_met,
+                                int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
+                                int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
+                                int64_t traj_pitch, rcbf_aql_plan** out) {
     if (!q || !out) return RCBF_E_NULL;
     *out = nullptr;
     if (int e = check_prm(prm)) return e;
@@ -371,6 +431,14 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
     if (prior_cols && prm->mode == RCBF_MODE_SIMULATED_CARS && mu) return RCBF_E_BAD_SHAPE;
     if (span_out && (((uintptr_t)span_out) & 15)) return RCBF_E_BAD_SHAPE;
     if (span_out && prm->solver != RCBF_SOLVER_ACTIVE_SET) return RCBF_E_BAD_MODE;
+    // the trajectory contract (rcbf_hip.h)
+    if (traj_mask & ~kTrajAll) return RCBF_E_BAD_MODE;
+    if (traj_mask && span_out) return RCBF_E_BAD_MODE;
+    if (!goal_met) traj_mask &= ~RCBF_TRAJ_GOAL_MET;  // a null pointer is not recorded, and never advanced
+    if (!status_out) traj_mask &= ~RCBF_TRAJ_STATUS;
+    if (!traj_mask) traj_pitch = 0;
+    if (traj_mask && (traj_pitch < B || traj_pitch % 4 != 0)) return RCBF_E_BAD_SHAPE;
+    if ((traj_mask & RCBF_TRAJ_OBS) && (((uintptr_t)obs_out) & 15)) return RCBF_E_BAD_SHAPE;
     // RCBF_AQL_PROFILE: a completion signal (timestamps) on every packet; RCBF_AQL_PROFILE_ENDS: on the first
     // and the last only, so the run is timed end to end without a signal between steps (each one adds
     // ~1.5 us to its step: profiles/r06/aql_dispatch_signal_cost)
@@ -395,22 +463,43 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
     constexpr int32_t kPerStepFlags =
         RCBF_AQL_PROFILE | RCBF_AQL_STUDY_MID_NOFENCE | RCBF_AQL_STUDY_MID_NOACQ | RCBF_AQL_STUDY_MID_NOREL |
         RCBF_AQL_PER_STEP;
+    const bool cars = mode == RCBF_MODE_SIMULATED_CARS;
+    const size_t ns = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NS : Dims<RCBF_MODE_UNICYCLE, 1>::NS;
+    const size_t no = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NO : Dims<RCBF_MODE_UNICYCLE, 1>::NO;
+    const size_t nu = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NU : Dims<RCBF_MODE_UNICYCLE, 1>::NU;
+    // bytes of one row of each output's (K, P, w) array; 0: not recorded (written in place)
+    const int64_t P = traj_pitch;
+    const int64_t row_obs = traj_mask & RCBF_TRAJ_OBS ? P * (int64_t)no * 4 : 0;
+    const int64_t row_u = traj_mask & RCBF_TRAJ_U ? P * (int64_t)nu * 4 : 0;
+    const int64_t row_rew = traj_mask & RCBF_TRAJ_REWARD ? P * 4 : 0;
+    const int64_t row_cost = traj_mask & RCBF_TRAJ_COST ? P * 4 : 0;
+    const int64_t row_done = traj_mask & RCBF_TRAJ_DONE ? P : 0;
+    const int64_t row_goal = traj_mask & RCBF_TRAJ_GOAL_MET ? P : 0;
+    const int64_t row_stat = traj_mask & RCBF_TRAJ_STATUS ? P * 4 : 0;
     const KernelInfo* kf = nullptr;
     if (q->fused && K > 1 && solver == RCBF_SOLVER_ACTIVE_SET && !span_out && !(flags & kPerStepFlags))
-        kf = find_kernel(q, safe_steps_prefix(mode, k, bs));
-    if (kf && kf->kernarg_bytes != sizeof(SafeStepsArgs)) kf = nullptr;
+        kf = traj_mask ? (q->traj ? find_kernel(q, safe_steps_traj_prefix(mode, k, bs)) : nullptr)
+                       : find_kernel(q, safe_steps_prefix(mode, k, bs));
+    if (kf && kf->kernarg_bytes != (traj_mask ? sizeof(SafeStepsTrajArgs) : sizeof(SafeStepsArgs))) kf = nullptr;
     if (kf) {
-        const bool cars = mode == RCBF_MODE_SIMULATED_CARS;
-        const size_t ns = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NS : Dims<RCBF_MODE_UNICYCLE, 1>::NS;
-        const size_t no = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NO : Dims<RCBF_MODE_UNICYCLE, 1>::NO;
-        const size_t nu = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NU : Dims<RCBF_MODE_UNICYCLE, 1>::NU;
         const size_t n = (size_t)B;
+        // a recorded output: the whole (K, P, w) array
+        auto ext = [K](int64_t row, size_t in_place) { return row ? (size_t)K * (size_t)row : in_place; };
         const struct {
             const void* p;
             size_t bytes;
-        } written[] = {{x, ns * n * 8},   {aux, n * 8},  {step, n * 4},     {episode, n * 4},
-                       {obs_out, no * n * 4}, {u_out, nu * n * 4}, {reward, n * 4}, {cost, n * 4},
-                       {done, n},          {goal_met, n}, {status_out, n * 4}, {fail_flag, 4}};
+        } written[] = {{x, ns * n * 8},
+                       {aux, n * 8},
+                       {step, n * 4},
+                       {episode, n * 4},
+                       {obs_out, ext(row_obs, no * n * 4)},
+                       {u_out, ext(row_u, nu * n * 4)},
+                       {reward, ext(row_rew, n * 4)},
+                       {cost, ext(row_cost, n * 4)},
+                       {done, ext(row_done, n)},
+                       {goal_met, ext(row_goal, n)},
+                       {status_out, ext(row_stat, n * 4)},
+                       {fail_flag, 4}};
         for (int32_t j = 0; j < n_u_rl && kf; ++j)
             for (const auto& w : written)
                 if (overlaps(u_rl_seq[j], nu * n * 4, w.p, w.bytes)) {
@@ -431,9 +520,14 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
     int rc = (int)hipMalloc(&p->kernargs, host.size());
     if (kf) std::memcpy(host.data() + table_off, u_rl_seq, (size_t)n_u_rl * sizeof(const float*));
     for (int32_t j = 0; j < npkt && !rc; ++j) {
+        // the row the packet's first step writes of every recorded output: chunk j starts at step j kFusedChunk
+        const int64_t r0 = kf ? (int64_t)j * kFusedChunk : (int64_t)j;
         if (kf) {
-            SafeStepsArgs a;
-            std::memset(&a, 0, sizeof a);
+            SafeStepsTrajArgs ta;
+            std::memset(&ta, 0, sizeof ta);
+            SafeStepsArgs& a = ta.s;
+            ta.traj_mask = traj_mask;
+            ta.traj_pitch = traj_pitch;
             a.B = B;
             a.x = x;
             a.aux = aux;
@@ -442,13 +536,13 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
             a.episode = episode;
             a.mu = mu;
             a.sigma = sigma;
-            a.obs_out = obs_out;
-            a.u_out = u_out;
-            a.reward = reward;
-            a.cost = cost;
-            a.done = done;
-            a.goal_met = goal_met;
-            a.status_out = status_out;
+            a.obs_out = rows_on(obs_out, r0, row_obs);
+            a.u_out = rows_on(u_out, r0, row_u);
+            a.reward = rows_on(reward, r0, row_rew);
+            a.cost = rows_on(cost, r0, row_cost);
+            a.done = rows_on(done, r0, row_done);
+            a.goal_met = rows_on(goal_met, r0, row_goal);
+            a.status_out = rows_on(status_out, r0, row_stat);
             a.fail_flag = fail_flag;
             a.auto_reset = auto_reset;
             a.seed = seed;
@@ -459,7 +553,8 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
             // chunk j: steps j kFusedChunk ... of the plan; its first step reads u_rl_seq[that index % n_u_rl]
             a.steps = std::min<int32_t>(kFusedChunk, K - j * kFusedChunk);
             a.ju0 = (int32_t)(((int64_t)j * kFusedChunk) % n_u_rl);
-            std::memcpy(host.data() + (size_t)j * kArgStride, &a, sizeof a);
+            // k_safe_steps reads the first sizeof(SafeStepsArgs) bytes, k_safe_steps_traj all of it
+            std::memcpy(host.data() + (size_t)j * kArgStride, &ta, sizeof ta);
             continue;
         }
         SafeStepArgs a;
@@ -472,13 +567,13 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
         a.episode = episode;
         a.mu = mu;
         a.sigma = sigma;
-        a.obs_out = obs_out;
-        a.u_out = u_out;
-        a.reward = reward;
-        a.cost = cost;
-        a.done = done;
-        a.goal_met = goal_met;
-        a.status_out = status_out;
+        a.obs_out = rows_on(obs_out, r0, row_obs);
+        a.u_out = rows_on(u_out, r0, row_u);
+        a.reward = rows_on(reward, r0, row_rew);
+        a.cost = rows_on(cost, r0, row_cost);
+        a.done = rows_on(done, r0, row_done);
+        a.goal_met = rows_on(goal_met, r0, row_goal);
+        a.status_out = rows_on(status_out, r0, row_stat);
         a.fail_flag = fail_flag;
         a.auto_reset = auto_reset;
         a.seed = seed;
@@ -539,6 +634,29 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
     }
     *out = p;
     return 0;
+}
+
+int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                            int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
+                            const float* mu, const float* sigma, int32_t prior_cols, float* obs_out, float* u_out,
+                            float* reward, float* cost, uint8_t* done, uint8_t* goal_met, int32_t* status_out,
+                            int32_t* fail_flag, int32_t auto_reset, uint64_t seed, int64_t env_offset,
+                            uint64_t* span_out, int32_t flags, rcbf_aql_plan** out) {
+    return build_safe_step_plan(q, prm, B, K, x, aux, step, episode, u_rl_seq, n_u_rl, mu, sigma, prior_cols, obs_out,
+                                u_out, reward, cost, done, goal_met, status_out, fail_flag, auto_reset, seed,
+                                env_offset, span_out, flags, 0, 0, out);
+}
+
+int rcbf_aql_safe_step_traj_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                                 int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
+                                 const float* mu, const float* sigma, int32_t prior_cols, float* obs_out,
+                                 float* u_out, float* reward, float* cost, uint8_t* done, uint8_t* goal_met,
+                                 int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
+                                 int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
+                                 int64_t traj_pitch, rcbf_aql_plan** out) {
+    return build_safe_step_plan(q, prm, B, K, x, aux, step, episode, u_rl_seq, n_u_rl, mu, sigma, prior_cols, obs_out,
+                                u_out, reward, cost, done, goal_met, status_out, fail_flag, auto_reset, seed,
+                                env_offset, span_out, flags, traj_mask, traj_pitch, out);
 }
 
 }  // extern "C"

@@ -130,6 +130,14 @@ __device__ __forceinline__ void st_out4(gptr<float> p, float4 v) {
     }
 }
 
+// ... as a plain store (no `nt`): the line is written once and not again, as the rows of a recorded
+// observation array are (k_safe_steps_traj; the flavour there is a measured choice, RCBF_TRAJ_OBS_PLAIN)
+__device__ __forceinline__ void st_out4_plain(gptr<float> p, float4 v) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 w = {v.x, v.y, v.z, v.w};
+    *reinterpret_cast<gptr<f4>>(p) = w;
+}
+
 // 16-byte f64 pair store (env state pairs)
 __device__ __forceinline__ void st_out2d(double* p, double a, double b) {
     typedef double d2 __attribute__((ext_vector_type(2)));

@@ -19,6 +19,14 @@
 #ifndef RCBF_KARG_PREFETCH
 #define RCBF_KARG_PREFETCH 0
 #endif
+// 1: k_safe_steps_traj stores the staged observation chunks as plain stores; 0 (the product): `nt`, as
+// k_safe_steps does.  Nothing rewrites a recorded row, so `nt` is not the obvious choice there; measured
+// (B = 65 536, all fields; profiles/r09/obs_store_flavour_traj_r09b.txt): `nt` 2.21 against plain 2.54 us per
+// step at 20 cars steps and 3.21 / 3.31 (20), 2.49 / 2.53 (1 000) for the unicycle at k = 5, plain ahead only
+// at 1 000 cars steps (1.90 against 1.95), five runs a side and the sets disjoint each time: `nt`.
+#ifndef RCBF_TRAJ_OBS_PLAIN
+#define RCBF_TRAJ_OBS_PLAIN 0
+#endif
 // 1: the cars step stores the state pairs that do not depend on the safe
 // action before the layer's chain runs (k_safe_step; 3.86 -> 3.67 us per
 // step, profiles/r03/early_store_confirm_r03k.txt); 0: after it
@@ -103,8 +111,9 @@ __device__ __forceinline__ void store_obs32(OP obs, int64_t i, const double* xs,
 // chunks, chunk c by lane c % 64.  Every chunk is read from LDS first, then
 // stored: the write-through store is an asm with a memory clobber, which
 // would otherwise hold each following LDS read (and its wait) behind the
-// previous store.  SC1: the chunks leave write-through (st_out4).
-template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*>
+// previous store.  SC1: the chunks leave write-through (st_out4); PLAIN_ST (gptr only): as plain stores.
+template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*,
+          bool PLAIN_ST = false>
 __device__ __forceinline__ void store_obs_chunks(OP obs, int64_t base, const float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
     __builtin_amdgcn_wave_barrier();
@@ -121,7 +130,12 @@ __device__ __forceinline__ void store_obs_chunks(OP obs, int64_t base, const flo
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int c = j * 64 + lane;
-        if (CH % 64 == 0 || c < CH) st_out4<SC1>(dst + 4 * c, chunk[j]);
+        if (CH % 64 == 0 || c < CH) {
+            if constexpr (PLAIN_ST)
+                st_out4_plain(dst + 4 * c, chunk[j]);
+            else
+                st_out4<SC1>(dst + 4 * c, chunk[j]);
+        }
     }
 }
 
@@ -130,7 +144,8 @@ __device__ __forceinline__ void store_obs_chunks(OP obs, int64_t base, const flo
 // store the block as 16-byte chunks, chunk c by lane c%64 -- every store
 // instruction covers whole contiguous lines (cars: 3 dwordx4 instead of 5
 // strided dwordx2).  Partial or unaligned waves take the per-lane path.
-template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*>
+template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*,
+          bool PLAIN_ST = false>
 __device__ __forceinline__ void store_obs32_staged(OP obs, int64_t i, int64_t B, const double* xs,
                                                    const double* obs_cache, float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
@@ -161,7 +176,7 @@ __device__ __forceinline__ void store_obs32_staged(OP obs, int64_t i, int64_t B,
 #pragma unroll
         for (int k = 0; k < NO; ++k) lds_wave[lane * NO + k] = (float)o[k];
     }
-    store_obs_chunks<MODE, WT, SC1>(obs, base, lds_wave, lane);
+    store_obs_chunks<MODE, WT, SC1, OP, PLAIN_ST>(obs, base, lds_wave, lane);
 }
 
 // One fused safe step of env i, from its state and inputs in registers (xs, a,
@@ -175,9 +190,9 @@ __device__ __forceinline__ void store_obs32_staged(OP obs, int64_t i, int64_t B,
 // dispatch): one source for both.  wt_lds: the write-through staging block of
 // the RCBF_WT_OUT study build.  GP: the buffers come as gptr (k_safe_steps), so every access is a global_*
 // instruction by type; k_safe_step passes its kernel arguments as they are.  OBS_SC1: the staged observation
-// chunks' store flavour (st_out4).
+// chunks' store flavour (st_out4); OBS_PLAIN: plain stores instead (k_safe_steps_traj's study switch).
 template <int SOLVER, int MODE, int K, bool ST, bool WT, bool GP = false,
-          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS>
+          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, bool OBS_PLAIN = false>
 __device__ __forceinline__ void safe_step_body(
     const rcbf_params& prm, int64_t B, int64_t i, ptr_g<GP, double> __restrict__ x, ptr_g<GP, double> __restrict__ aux,
     ptr_g<GP, int32_t> __restrict__ step, ptr_g<GP, uint32_t> __restrict__ episode,
@@ -268,7 +283,7 @@ __device__ __forceinline__ void safe_step_body(
             st_out(&step[i], st);
         }
     }
-    store_obs32_staged<MODE, WT, OBS_SC1>(obs_out, i, B, xs, oc, obs_stage, lane);
+    store_obs32_staged<MODE, WT, OBS_SC1, ptr_g<GP, float>, OBS_PLAIN>(obs_out, i, B, xs, oc, obs_stage, lane);
     if constexpr (WT) {
         constexpr int NU4 = 4 * D::NU;
         float ufc[D::NU];
@@ -444,9 +459,11 @@ __global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict_
 // vector spill and no scratch (tests/test_abi_fused_cpu.py).  Cars fits (168 VGPRs, 106 SGPRs) and so does
 // the unicycle at k = 1; written plain, the unicycle at k = 2, 3, 4, 5, 6 spills 2, 6, 8, 12, 8 scalar
 // registers (256-thread workgroups).
-template <int MODE, int K>
+// TRAJ (k_safe_steps_traj): no kernel is plain.  With the recorded outputs' pointers changing every step the
+// cars kernel and the unicycle at k = 1, written plain, spill 5 and 2 scalar registers (64-thread workgroups).
+template <int MODE, int K, bool TRAJ = false>
 constexpr bool fused_plain() {
-    return MODE == RCBF_MODE_SIMULATED_CARS || K == 1;
+    return !TRAJ && (MODE == RCBF_MODE_SIMULATED_CARS || K == 1);
 }
 
 // Argument block of k_safe_steps, at the offsets of its parameter list (the
@@ -500,6 +517,56 @@ static_assert(offsetof(SafeStepsArgs, auto_reset) == 128 && offsetof(SafeStepsAr
 // workgroup size and lane-to-env map as k_safe_step; the exact solver only.
 // The argument block (SafeStepsArgs above) keeps k_safe_step's offsets, with
 // the table in u_rl's place.
+//
+// k_safe_steps_traj (the trajectory form, rcbf_aql_safe_step_traj_plan): the same loop, which after every
+// step moves each RECORDED output's pointer on by one row of its dense (steps, P, w) array, P = traj_pitch
+// envs, w the output's per-env width: step j's values stay at [j][i] instead of being overwritten by step
+// j + 1.  traj_mask (RCBF_TRAJ_*, rcbf_hip.h) says which outputs are recorded; the others, and x, aux, step,
+// episode, fail_flag always, are written in place as in k_safe_steps.  The builder clears the bit of a null
+// pointer (a null pointer moved on is no longer null to the step's `if (goal_met)`), and checks P >= B,
+// P % 4 == 0 and a 16-byte aligned recorded obs base, which keep every 16-byte observation chunk aligned in
+// every row (store_obs_chunks).  Its argument block is SafeStepsArgs followed by traj_mask and traj_pitch:
+struct SafeStepsTrajArgs {
+    SafeStepsArgs s;
+    int32_t traj_mask;
+    int64_t traj_pitch;
+};
+static_assert(offsetof(SafeStepsTrajArgs, traj_mask) == 408 && offsetof(SafeStepsTrajArgs, traj_pitch) == 416 &&
+                  sizeof(SafeStepsTrajArgs) == 424,
+              "kernarg layout");
+
+// traj_mask and traj_pitch as the loop carries them (k = 8: this wave's copy in LDS)
+struct TrajTail {
+    int64_t pitch;
+    int32_t mask;
+    int32_t pad;
+};
+
+// ... read from k_safe_steps_traj's argument segment, `off` (0, or a zero the compiler cannot see through)
+// bytes on: uniform loads from the constant address space, so scalar loads wherever they stand
+__device__ __forceinline__ TrajTail traj_from_kernargs(uint32_t off) {
+    TrajTail t{0, 0, 0};
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const char __attribute__((address_space(4)))* cbytes_t;
+    const cbytes_t ka = (cbytes_t)__builtin_amdgcn_kernarg_segment_ptr() + off;
+    t.mask = *reinterpret_cast<const int32_t __attribute__((address_space(4)))*>(
+        ka + offsetof(SafeStepsTrajArgs, traj_mask));
+    t.pitch = *reinterpret_cast<const int64_t __attribute__((address_space(4)))*>(
+        ka + offsetof(SafeStepsTrajArgs, traj_pitch));
+#endif
+    return t;
+}
+
+template <int BS>
+__device__ __forceinline__ TrajTail* traj_stage_of(int wave) {
+    __shared__ TrajTail stage[BS / 64];
+    return &stage[wave];
+}
+
+// The loop's source is one file, rcbf_safe_steps_loop.inc, included as the body of both kernels: with TRAJ =
+// false every `if constexpr (TRAJ)` in it is discarded and k_safe_steps is, statement for statement, the
+// kernel it was before the trajectory form existed (and compiles to the same machine code, which a common
+// device function inlined into it did not: the inlined copy came out with other branches and registers).
 template <int MODE, int K, int BS = kBlock>
 __global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict__ x, double* __restrict__ aux,
                                                        int32_t* __restrict__ step,
@@ -512,186 +579,24 @@ __global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict
                                                        int32_t* __restrict__ status_out, int32_t* fail_flag,
                                                        int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
                                                        int prior_cols, int n_u, int steps, int ju0) {
-    using D = Dims<MODE, K>;
-    constexpr int SOLVER = RCBF_SOLVER_ACTIVE_SET;
-    constexpr bool WT = false;
-    constexpr bool PLAIN = fused_plain<MODE, K>();
-    // the staged observation chunks leave `nt` here, cars included: no kernel end follows a step, the next
-    // step rewrites the line, and `sc1` would write each step's chunks through to HBM (measured: DESIGN 5.2)
-    constexpr bool OBS_SC1 = false;
-    int64_t i = env_index<BS>();
-    if (i >= B) return;
-    double xs[D::NS];
-    load_state<MODE>(x, B, i, xs);
-    double a = ld_in(&aux[i]);
-    int st = ld_in(&step[i]);
-    // The u_RL table, read with scalar loads: its address, ju0, n_u and steps are the same for every lane,
-    // and nothing writes it while a plan runs, which its type says (the constant address space: a uniform
-    // load from it is a scalar load wherever it stands among the loop's stores).  Its entries are addresses
-    // of global memory, and are typed so (gptr, rcbf_common.hpp).
-    typedef const uint64_t __attribute__((address_space(4)))* ctab_t;
-    const ctab_t tab = (ctab_t)reinterpret_cast<const uint64_t*>(u_tab);
-    float us[D::NU], m[D::NS], s[D::NS];
-    {
-        const gptr<const float> u0 = reinterpret_cast<gptr<const float>>(tab[ju0]);
-#pragma unroll
-        for (int c = 0; c < D::NU; ++c) us[c] = ld_in(&u0[i * D::NU + c]);
-    }
-    // env i's episode counter, which only this lane writes (at a reset): read once, then kept in a register
-    uint32_t epr = episode ? ld_in(&episode[i]) : 0u;
-    // step 1's buffer: every step issues the load of the next step's action from an address that the step
-    // before it fetched, so neither the table entry nor the action is ever waited for where it is asked for
-    int ju = ju0 + 1 == n_u ? 0 : ju0 + 1;
-    gptr<const float> u_next = reinterpret_cast<gptr<const float>>(tab[ju]);
-    if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) prefetch_kernargs<7>();
-    // the priors: inputs of the plan that nothing in a run writes, loaded once (k_safe_step's layouts)
-    if (prior_cols) {
-#pragma unroll
-        for (int k = 0; k < D::NS; ++k) {
-            m[k] = 0.0f;
-            s[k] = prior_sigma<MODE>(k);
-        }
-        if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) {
-            if (sigma) {
-                s[5] = ld_in(&sigma[i]);
-                s[7] = ld_in(&sigma[B + i]);
-                s[9] = ld_in(&sigma[2 * B + i]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < D::NS; ++k) {
-                if (mu) m[k] = ld_in(&mu[k * B + i]);
-                if (sigma) s[k] = ld_in(&sigma[k * B + i]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < D::NS; ++k) {
-            m[k] = mu ? mu[i * D::NS + k] : 0.0f;
-            s[k] = sigma ? sigma[i * D::NS + k] : prior_sigma<MODE>(k);
-        }
-    }
-    __shared__ float obs_stage[BS / 64][64 * D::NO];
-    // k = 8 only: the parameter block, one copy per wave, written by every live lane of the wave (the same
-    // values; a wave's LDS operations execute in order, so its reads below see them)
-    __shared__ rcbf_params prm_stage[K >= 8 ? BS / 64 : 1];
-    if constexpr (K >= 8) {
-        prm_stage[threadIdx.x >> 6] = prm;
-        __builtin_amdgcn_wave_barrier();
-    }
-    const Stamps<false> stamps{};
-    // Register budget of the loop.  Whatever the body derives from loop-invariant values alone (null
-    // tests and per-lane addresses of the 15 buffers, the 60 dwords of the parameter block, the loop's
-    // own counters) the compiler hoists out of the loop, where it stays live over the whole body on top
-    // of what one step needs.  Where that fits (PLAIN, fused_plain above) the loop is written as it reads.
-    // The unicycle step alone takes every scalar register there is, and at 7 and 8 hazards every vector
-    // register: there everything the loop carries beside the env's state lives in accumulation registers
-    // (the unified file has room), as uniform per-lane values behind empty asm copies the compiler cannot
-    // see through; no instruction is emitted for a copy, a use costs one register read.  Every step then
-    // derives from them what k_safe_step derives once per dispatch, and the parameter block is read from
-    // the argument segment again (scalar loads that hit the scalar cache; vector loads at k = 8).  The
-    // walk of the table stays scalar: the wave-uniform values are read back with readfirstlane.  In both
-    // forms the buffers are gptr, so every access is a global_* instruction.  No kernel spills.
-    int64_t Bv = B;
-    gptr<double> xv = (gptr<double>)x;
-    gptr<double> auxv = (gptr<double>)aux;
-    gptr<int32_t> stepv = (gptr<int32_t>)step;
-    gptr<uint32_t> epv = (gptr<uint32_t>)episode;
-    gptr<float> obsv = (gptr<float>)obs_out;
-    gptr<float> uv = (gptr<float>)u_out;
-    gptr<float> rewv = (gptr<float>)reward;
-    gptr<float> costv = (gptr<float>)cost;
-    gptr<uint8_t> donev = (gptr<uint8_t>)done;
-    gptr<uint8_t> goalv = (gptr<uint8_t>)goal_met;
-    gptr<int32_t> statv = (gptr<int32_t>)status_out;
-    gptr<int32_t> failv = (gptr<int32_t>)fail_flag;
-    uint64_t tabv = reinterpret_cast<uint64_t>(u_tab), unextv = reinterpret_cast<uint64_t>(u_next);
-    int arv = auto_reset, lanev = threadIdx.x & 63, nuv = n_u, juv = ju, leftv = steps,
-        widv = threadIdx.x >> 6;
-    uint64_t seedv = seed;
-    int64_t offv = off;
-#define RCBF_OPAQUE_V()                                                                                          \
-    if constexpr (!PLAIN) {                                                                                      \
-        asm volatile("" : "+a"(xv), "+a"(auxv), "+a"(stepv), "+a"(epv), "+a"(obsv), "+a"(uv), "+a"(rewv));     \
-        asm volatile("" : "+a"(costv), "+a"(donev), "+a"(goalv), "+a"(statv), "+a"(failv), "+a"(epr),         \
-                     "+a"(Bv), "+a"(arv), "+a"(lanev), "+a"(i));                                                 \
-        asm volatile("" : "+a"(widv), "+a"(tabv), "+a"(nuv), "+a"(juv), "+a"(leftv), "+a"(seedv), "+a"(offv),   \
-                     "+a"(unextv));                                                                              \
-    }
-    RCBF_OPAQUE_V();  // once: uniform values, kept in accumulation registers from here on
-    // Everything loaded so far has arrived before the loop is entered (vmcnt(0); expcnt and lgkmcnt left
-    // alone).  A wait for one of these loads inside the loop would be passed again in every step, where all
-    // it can wait for is the last step's stores.
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-#pragma nounroll
-    while (leftv > 0) {
-        RCBF_OPAQUE_V();  // every step: nothing derived from them is loop-invariant to the compiler
-        const rcbf_params* prm_p = &prm;
-        if constexpr (!PLAIN) {
-#pragma unroll
-            for (int k = 0; k < D::NS; ++k) asm volatile("" : "+a"(m[k]), "+a"(s[k]));  // the priors too
-            if constexpr (K >= 8) {
-                // k = 8: the step's scalar registers are all taken, so its parameters are read per lane, from
-                // this wave's copy in LDS (prm_stage; behind a per-lane zero the compiler cannot see through,
-                // which keeps the LDS provenance: ds_read).  Vector loads from the argument segment would count
-                // in vmcnt behind the last step's stores, and waiting for them would wait for those.
-                uint32_t prm_voff = 0;
-                asm volatile("" : "+v"(prm_voff));
-                prm_p = reinterpret_cast<const rcbf_params*>(reinterpret_cast<const char*>(&prm_stage[widv]) +
-                                                             prm_voff);
-            } else {
-                uint32_t prm_off = 0;
-                asm volatile("" : "+s"(prm_off));
-                prm_p = reinterpret_cast<const rcbf_params*>(reinterpret_cast<const char*>(&prm) + prm_off);
-            }
-        }
-        const rcbf_params& prm_j = *prm_p;
-        // the next step's action, issued ahead of this step's chain from the address the last step fetched
-        float un[D::NU];
-#pragma unroll
-        for (int c = 0; c < D::NU; ++c) un[c] = 0.0f;
-        --leftv;
-        if (leftv > 0) {
-            const gptr<const float> u1 = reinterpret_cast<gptr<const float>>(unextv);
-#pragma unroll
-            for (int c = 0; c < D::NU; ++c) un[c] = ld_in(&u1[i * D::NU + c]);
-        }
-        // the address of the buffer of the step after the next: a scalar load (an entry of the table whether
-        // or not that step runs), whose result is first needed at the end of this step
-        uint64_t unext2;
-        {
-            int nu_s = n_u, ju_s = juv;
-            uint64_t tab_s = reinterpret_cast<uint64_t>(u_tab);
-            if constexpr (!PLAIN) {
-                // out of their accumulation registers, as the wave-uniform values they are
-                tab_s = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(tabv >> 32)) << 32) |
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tabv);
-                nu_s = __builtin_amdgcn_readfirstlane(nuv);
-                ju_s = __builtin_amdgcn_readfirstlane(juv);
-            }
-            ju_s = ju_s + 1 == nu_s ? 0 : ju_s + 1;
-            juv = ju_s;
-            unext2 = reinterpret_cast<ctab_t>(tab_s)[ju_s];
-        }
-        bool rs = false;
-        safe_step_body<SOLVER, MODE, K, false, WT, true, OBS_SC1>(prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv,
-                                                                  costv, donev, goalv, statv, failv, arv, seedv, offv,
-                                                                  xs, a, st, us, m, s, epv != nullptr, epr, stamps,
-                                                                  obs_stage[widv], nullptr, lanev, &rs);
-        epr += rs ? 1u : 0u;  // a reset stored epr + 1
-        // this step's chunk reads of obs_stage stay ahead of the next step's writes to it (one wave's LDS
-        // operations execute in order; this keeps the compiler from reordering them)
-        __builtin_amdgcn_wave_barrier();
-        // every step's stores are made in that step: without this the compiler, which sees in the plain form
-        // that a step overwrites what the last one stored to aux, step, u, reward, cost and done, keeps those
-        // in registers and stores them once after the loop (no instruction, no wait: a compiler barrier)
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int c = 0; c < D::NU; ++c) us[c] = un[c];
-        if constexpr (!PLAIN) asm volatile("" : "+s"(unext2));  // a scalar load's result, scalar till here
-        unextv = unext2;
-    }
-#undef RCBF_OPAQUE_V
+    constexpr bool TRAJ = false;
+#include "rcbf_safe_steps_loop.inc"
+}
+
+// The trajectory form (SafeStepsTrajArgs above).  traj_mask and traj_pitch are part of the argument block and
+// read from it by the loop where it uses them, not through these two parameters.
+template <int MODE, int K, int BS = kBlock>
+__global__ void __launch_bounds__(BS) k_safe_steps_traj(
+    int64_t B, double* __restrict__ x, double* __restrict__ aux, int32_t* __restrict__ step,
+    const float* const* __restrict__ u_tab, uint32_t* __restrict__ episode, const float* __restrict__ mu,
+    const float* __restrict__ sigma, float* __restrict__ obs_out, float* __restrict__ u_out,
+    float* __restrict__ reward, float* __restrict__ cost, uint8_t* __restrict__ done, uint8_t* __restrict__ goal_met,
+    int32_t* __restrict__ status_out, int32_t* fail_flag, int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
+    int prior_cols, int n_u, int steps, int ju0, int32_t traj_mask, int64_t traj_pitch) {
+    (void)traj_mask;
+    (void)traj_pitch;
+    constexpr bool TRAJ = true;
+#include "rcbf_safe_steps_loop.inc"
 }
 
 // Explicit instantiation of k_safe_steps for every mode / hazard count and
@@ -706,5 +611,17 @@ __global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict
     RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, 64);  \
     RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, 128); \
     RCBF_SAFE_STEPS_INSTANTIATE_BS(MODE_, K_, 256)
+
+// ... and of k_safe_steps_traj: the same 27
+#define RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, BS_)                                                         \
+    template __global__ void k_safe_steps_traj<MODE_, K_, BS_>(                                                     \
+        int64_t, double* __restrict__, double* __restrict__, int32_t* __restrict__, const float* const* __restrict__, \
+        uint32_t* __restrict__, const float* __restrict__, const float* __restrict__, float* __restrict__,          \
+        float* __restrict__, float* __restrict__, float* __restrict__, uint8_t* __restrict__, uint8_t* __restrict__, \
+        int32_t* __restrict__, int32_t*, int, uint64_t, int64_t, rcbf_params, int, int, int, int, int32_t, int64_t)
+#define RCBF_SAFE_STEPS_TRAJ_INSTANTIATE(MODE_, K_)      \
+    RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, 64);  \
+    RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, 128); \
+    RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, 256)
 
 }  // namespace rcbf

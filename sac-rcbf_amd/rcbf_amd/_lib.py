@@ -122,6 +122,10 @@ SIGNATURES = {
     "rcbf_aql_kernel_count": [_P],
     "rcbf_aql_safe_step_plan": [_P, _PRM, _I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _I32, _U64, _I64, _P, _I32, ctypes.POINTER(ctypes.c_void_p)],
+    # ... + traj_mask, traj_pitch
+    "rcbf_aql_safe_step_traj_plan": [_P, _PRM, _I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _I32, _U64, _I64, _P, _I32, _I32, _I64,
+                                     ctypes.POINTER(ctypes.c_void_p)],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],

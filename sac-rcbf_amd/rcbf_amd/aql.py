@@ -16,6 +16,14 @@ re-load between two dispatches.  `plan.dispatches` tells which form a plan
 took (K: per step; 1 per 4096 steps: fused); `fused=False`, a span buffer,
 `profile=True` or a u_RL buffer that overlaps an output keep the per-step form.
 
+A TRAJECTORY plan (`trajectory=True`, or a dict from
+`BatchedEnv.make_trajectory`) keeps every step's outputs: step j writes row j
+of each recorded field's (K, B[, w]) array instead of overwriting the one
+(B[, w]) buffer -- what the warm-up phase (main.py:88-107) and evaluation
+rollouts need from steps whose actions are known beforehand.  It takes the
+same two forms (fused: the k_safe_steps_traj kernels).  `plan.trajectory` is
+the dict; after `run()` the env and the outputs dict are as after a plain plan.
+
 The queue is not a HIP stream: `run()` first waits for all HIP work queued
 on the env's device unless `sync_hip=False` is
 passed by a caller that has synchronised itself (bench.py's timed region
@@ -31,6 +39,10 @@ from . import _lib
 PROFILE = 1  # RCBF_AQL_PROFILE
 PROFILE_ENDS = 64  # RCBF_AQL_PROFILE_ENDS: timestamps of the first and last dispatch only
 PER_STEP = 128  # RCBF_AQL_PER_STEP: K dispatches even where the fused form applies
+# RCBF_TRAJ_*: the outputs a trajectory plan records
+TRAJ_OBS, TRAJ_U, TRAJ_REWARD, TRAJ_COST, TRAJ_DONE, TRAJ_GOAL_MET, TRAJ_STATUS = 1, 2, 4, 8, 16, 32, 64
+TRAJ_BITS = {"obs": TRAJ_OBS, "u": TRAJ_U, "reward": TRAJ_REWARD, "cost": TRAJ_COST, "done": TRAJ_DONE,
+             "goal_met": TRAJ_GOAL_MET, "status": TRAJ_STATUS}
 
 
 def _bind():
@@ -73,13 +85,20 @@ class AqlQueue:
         self._fin()
 
     def safe_step_plan(self, env, u_rl_seq, layer, steps=None, mean=None, sigma=None, outputs=None,
-                       auto_reset=True, prior_layout="rows", span=None, profile=False, fence_flags=0, fused=None):
+                       auto_reset=True, prior_layout="rows", span=None, profile=False, fence_flags=0, fused=None,
+                       trajectory=None):
         """K = steps (default len(u_rl_seq)) fused safe steps of `env` with
         `layer`, step j reading u_rl_seq[j % len(u_rl_seq)]: the same
         arguments and results as env.safe_step_seq (span: the measurement
         instantiation of env.safe_step_span, step j stamping span[j]).
         fused: None or True leave the plan's form to the library (fused where
-        it applies, see the module docstring); False asks for K dispatches."""
+        it applies, see the module docstring); False asks for K dispatches.
+        trajectory: None (a plain plan), True (record every field of
+        env.TRAJECTORY_FIELDS, allocated here) or a dict of (K', B[, w])
+        views, K' >= K, of pitch-padded arrays as env.make_trajectory
+        returns them, whose keys select the recorded fields: step j writes
+        row j of each (on a step that resets, obs[j] is the next episode's
+        first observation).  Not with span."""
         if env.device != self.device:
             raise ValueError(f"env on {env.device}, queue on {self.device}")
         o = outputs if outputs is not None else env.make_outputs()
@@ -105,36 +124,96 @@ class AqlQueue:
         a = env._step_args(layer, o, auto_reset)
         arr = (ctypes.c_void_p * len(us))(*[u.data_ptr() for u in us])
         h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(_lib.load().rcbf_aql_safe_step_plan(
-                self.handle, ctypes.byref(layer._prm), env.num_envs, K, *[v or None for v in a[2:6]], arr, len(us),
-                None if mean is None else mean.data_ptr(), None if sigma is None else sigma.data_ptr(), int(cols),
-                *[v or None for v in a[9:17]], *a[17:20], None if span is None else span.data_ptr(),
-                (PROFILE if profile else 0) | (PER_STEP if fused is False else 0) | int(fence_flags),
-                ctypes.byref(h)), "rcbf_aql_safe_step_plan")
+        flags = (PROFILE if profile else 0) | (PER_STEP if fused is False else 0) | int(fence_flags)
+        head = (self.handle, ctypes.byref(layer._prm), env.num_envs, K, *[v or None for v in a[2:6]], arr, len(us),
+                None if mean is None else mean.data_ptr(), None if sigma is None else sigma.data_ptr(), int(cols))
+        tail = (*a[17:20], None if span is None else span.data_ptr(), flags)
+        traj = None
+        if trajectory is not None and trajectory is not False:
+            if span is not None:
+                raise ValueError("a trajectory plan takes no span buffer")
+            traj = env.make_trajectory(K) if trajectory is True else dict(trajectory)
+            mask, pitch = _trajectory_args(env, traj, K)
+            # a[9:17]: obs, u, reward, cost, done, goal_met, status, fail_flag -- a recorded field's pointer is
+            # its array's base; the cars goal_met is never recorded (env._step_args passes none either)
+            outs = list(a[9:17])
+            for j, f in enumerate(("obs", "u", "reward", "cost", "done", "goal_met", "status")):
+                if mask & TRAJ_BITS[f]:
+                    outs[j] = traj[f].data_ptr()
+            with torch.cuda.device(self.device):
+                _check(_lib.load().rcbf_aql_safe_step_traj_plan(*head, *[v or None for v in outs], *tail, mask, pitch,
+                                                                ctypes.byref(h)), "rcbf_aql_safe_step_traj_plan")
+        else:
+            with torch.cuda.device(self.device):
+                _check(_lib.load().rcbf_aql_safe_step_plan(*head, *[v or None for v in a[9:17]], *tail,
+                                                           ctypes.byref(h)), "rcbf_aql_safe_step_plan")
         # the plan holds raw pointers: keep every tensor it reads or writes alive with it
-        keep = (env, layer, o, us, mean, sigma, span)
-        plan = AqlPlan(self, h, K, keep, bool(profile), env)
+        keep = (env, layer, o, us, mean, sigma, span, traj)
+        plan = AqlPlan(self, h, K, keep, bool(profile), env, traj)
         self._plans.add(plan)
         return plan
+
+
+def _trajectory_args(env, traj, K):
+    """(traj_mask, traj_pitch) of a trajectory dict for a K-step plan of
+    `env`, after checking every field: a known name, the field's dtype, on
+    the env's device, shape (K', B[, w]) with K' >= K, and the strides of a
+    [:, :B] view of a dense (K', P[, w]) array, one P for all fields."""
+    spec = env._trajectory_spec()
+    B = env.num_envs
+    mask, pitch = 0, None
+    cars = env.dynamics_mode == "SimulatedCars"
+    for f, t in traj.items():
+        if f not in spec:
+            raise ValueError(f"unknown trajectory field {f!r} (one of {sorted(spec)})")
+        w, dt = spec[f]
+        if not (torch.is_tensor(t) and t.dtype == dt and t.device == env.device):
+            raise ValueError(f"trajectory[{f!r}] must be a {dt} tensor on {env.device}")
+        want = (B, w) if w else (B,)
+        if t.dim() != len(want) + 1 or tuple(t.shape[1:]) != want or t.shape[0] < K:
+            raise ValueError(f"trajectory[{f!r}] must have shape (>= {K}, {', '.join(map(str, want))}), "
+                             f"got {tuple(t.shape)}")
+        ww = w or 1
+        st = t.stride()
+        if st[1:] != ((w, 1) if w else (1,)) or st[0] % ww or st[0] // ww < B:
+            raise ValueError(f"trajectory[{f!r}] must be a [:, :B] view of a dense (K, P{', w' if w else ''}) array "
+                             f"(use env.make_trajectory), got strides {st}")
+        p = st[0] // ww
+        if pitch is not None and p != pitch:
+            raise ValueError(f"trajectory[{f!r}] has row pitch {p}, the other fields {pitch}")
+        pitch = p
+        if f == "goal_met" and cars:
+            continue  # never met: stays as make_trajectory zero-filled it
+        mask |= TRAJ_BITS[f]
+    return mask, (pitch or 0)
 
 
 class AqlPlan:
     """K pre-built steps of the fused step (see AqlQueue.safe_step_plan)."""
 
-    def __init__(self, queue, handle, K, keep, profiled, env):
+    def __init__(self, queue, handle, K, keep, profiled, env, trajectory=None):
         self.queue, self.K, self.profiled = queue, K, profiled
         self._h, self._keep, self._env = handle, keep, env
+        self.trajectory = trajectory  # the dict of a trajectory plan (field -> (K', B[, w]) view), else None
         self._fin = weakref.finalize(self, _lib.load().rcbf_aql_plan_free, handle)
 
-    def run(self, sync_hip=True, timeout_us=0):
-        """Submit the K steps and return when they have completed."""
+    def run(self, sync_hip=True, timeout_us=0, copy_back=True):
+        """Submit the K steps and return when they have completed.  A
+        trajectory plan then copies row K - 1 of each recorded field into
+        env.obs / the outputs dict, which are then exactly as after a plain
+        plan (copy_back=False skips that, for timing)."""
         if sync_hip:
             torch.cuda.synchronize(self.queue.device)
         if not self._fin.alive or not self.queue._fin.alive:
             raise RuntimeError("the AQL plan (or its queue) was freed")
         # ctypes, not the CPython binding: a 20-step run measured the same through both (85.1 / 85.5 us, r06w)
         _check(_lib.load().rcbf_aql_run(self._h, timeout_us), "rcbf_aql_run")
+        if self.trajectory is not None and copy_back:
+            o = self._keep[2]
+            for f, t in self.trajectory.items():
+                dst = self._env.obs if f == "obs" else o.get(f)
+                if dst is not None and not (f == "goal_met" and self._env.dynamics_mode == "SimulatedCars"):
+                    dst.copy_(t[self.K - 1])
         return self._env.obs, self._keep[2]["reward"], self._keep[2]["done"], self._keep[2]
 
     @property

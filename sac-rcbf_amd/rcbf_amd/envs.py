@@ -427,6 +427,42 @@ class BatchedEnv:
                 "done": torch.empty(B, dtype=torch.uint8, device=d),
                 "goal_met": torch.empty(B, dtype=torch.uint8, device=d)}
 
+    TRAJECTORY_FIELDS = ("obs", "u", "reward", "cost", "done", "goal_met")
+
+    def _trajectory_spec(self):
+        """field -> (per-env width, 0 for a scalar field; dtype) of a trajectory
+        plan's recordable outputs (AqlQueue.safe_step_plan(trajectory=...))."""
+        return {"obs": (self.n_o, torch.float32), "u": (self.n_u, torch.float32), "reward": (0, torch.float32),
+                "cost": (0, torch.float32), "done": (0, torch.uint8), "goal_met": (0, torch.uint8),
+                "status": (0, torch.int32)}
+
+    def make_trajectory(self, K, fields=TRAJECTORY_FIELDS):
+        """Per-step output arrays for a K-step trajectory plan
+        (AqlQueue.safe_step_plan(..., trajectory=...)): each field of `fields`
+        (TRAJECTORY_FIELDS, or "status": the QP status, int32) as a (K, B[, w])
+        view of a dense (K, P[, w]) array, P = B rounded up to a multiple of 64
+        (every row of every field starts on a 16-byte boundary, which the
+        kernel's observation stores need); the pitch is stride(0) / w.  Step j
+        of the plan writes row j.  The cars env never meets a goal: its
+        goal_met is zero-filled here once and not recorded."""
+        B, d, K = self.num_envs, self.device, int(K)
+        if K <= 0:
+            raise ValueError(f"K must be positive, got {K}")
+        spec = self._trajectory_spec()
+        P = (B + 63) // 64 * 64
+        out = {}
+        for f in fields:
+            if f not in spec:
+                raise ValueError(f"unknown trajectory field {f!r} (one of {sorted(spec)})")
+            w, dt = spec[f]
+            shape = (K, P, w) if w else (K, P)
+            if f == "goal_met" and self.dynamics_mode == "SimulatedCars":
+                t = torch.zeros(shape, dtype=dt, device=d)
+            else:
+                t = torch.empty(shape, dtype=dt, device=d)
+            out[f] = t[:, :B]
+        return out
+
     def rollout(self, u_rl_seq, layer):
         """K fused safe steps in one launch (rcbf_safe_rollout) from a
         pre-sampled u_rl (K, B, n_u) f32, prior mean/sigma, auto-reset.
