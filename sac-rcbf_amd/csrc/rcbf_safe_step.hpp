@@ -33,6 +33,23 @@
 #ifndef RCBF_EARLY_STORE
 #define RCBF_EARLY_STORE 1
 #endif
+// What the cars fused loop (k_safe_steps, k_safe_steps_traj) carries from a step's tail into the next step:
+// 0: nothing, every step derives its layer's state from xs again (the per-step kernel's statements);
+// 1 (the product): the fp32 observation row the tail has just computed for its store, which is the row the
+//    next step's layer would compute again from the same xs;
+// 2 (study): that row, and the next step's raw rows, built from it in the tail behind the LDS writes of the
+//    observation staging instead of at the head of the next step's chain.  Slower than 1 in every leg of the
+//    A/B (profiles/r10/ab_carry_vs_parent_r10a.txt): at the head the rows' arithmetic runs between the env's
+//    pre-step fp64 chain, in the tail it only lengthens a stretch that has independent work already.
+#ifndef RCBF_FUSED_CARRY
+#define RCBF_FUSED_CARRY 1
+#endif
+// With the rows carried (RCBF_FUSED_CARRY == 2) the head of a step has nothing to build before it can solve.
+// 0: the env's pre-step part and the early stores first, then the solve, as in the per-step kernel; 1: the
+// solve first (the faster of the two with carried rows, same file; neither reaches RCBF_FUSED_CARRY == 1).
+#ifndef RCBF_FUSED_CARRY_SOLVE_FIRST
+#define RCBF_FUSED_CARRY_SOLVE_FIRST 0
+#endif
 
 namespace rcbf {
 
@@ -113,7 +130,7 @@ __device__ __forceinline__ void store_obs32(OP obs, int64_t i, const double* xs,
 // would otherwise hold each following LDS read (and its wait) behind the
 // previous store.  SC1: the chunks leave write-through (st_out4); PLAIN_ST (gptr only): as plain stores.
 template <int MODE, bool WT = false, bool SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, typename OP = float*,
-          bool PLAIN_ST = false>
+          bool PLAIN_ST = false, bool WHOLE = false>
 __device__ __forceinline__ void store_obs_chunks(OP obs, int64_t base, const float* lds_wave, int lane) {
     constexpr int NO = Dims<MODE, 1>::NO;
     __builtin_amdgcn_wave_barrier();
@@ -122,6 +139,31 @@ __device__ __forceinline__ void store_obs_chunks(OP obs, int64_t base, const flo
     const OP dst = obs + base * NO;
     constexpr int NJ = (CH + 63) / 64;
     float4 chunk[NJ];
+    if constexpr (WHOLE) {
+        // The cars fused loop's form: the first CH / 64 chunks are whole in the source, and the remainder
+        // chunk's LDS read is unconditional too (a lane past the block reads its own first chunk again and
+        // stores nothing), so that one lane test stands around one store and the reads share one wait.
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = j * 64 + lane;
+            chunk[j] = src[(j < CH / 64 || c < CH) ? c : lane];
+        }
+        // every read is issued before the first store (nothing is emitted: the compiler otherwise moves the
+        // remainder chunk's read, and a wait of its own, in behind the lane test)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(chunk[j].x), "+v"(chunk[j].y), "+v"(chunk[j].z), "+v"(chunk[j].w));
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = j * 64 + lane;
+            if (j < CH / 64 || c < CH) {
+                if constexpr (PLAIN_ST)
+                    st_out4_plain(dst + 4 * c, chunk[j]);
+                else
+                    st_out4<SC1>(dst + 4 * c, chunk[j]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int c = j * 64 + lane;
@@ -179,6 +221,36 @@ __device__ __forceinline__ void store_obs32_staged(OP obs, int64_t i, int64_t B,
     store_obs_chunks<MODE, WT, SC1, OP, PLAIN_ST>(obs, base, lds_wave, lane);
 }
 
+// The first half of store_obs32_staged for a caller that already holds the fp32 observation row (the cars
+// fused loop, which carries it into the next step): a full wave writes its 64 rows to LDS and returns true
+// -- the caller calls store_obs_chunks later, after whatever it has to issue behind the LDS writes -- a
+// partial or unaligned wave stores its row per lane, as store_obs32 does, and returns false.
+template <int MODE, typename OP>
+__device__ __forceinline__ bool stage_obs32_row(OP obs, int64_t i, int64_t B, const float* o32, float* lds_wave,
+                                                int lane) {
+    constexpr int NO = Dims<MODE, 1>::NO;
+    static_assert(NO % 2 == 0, "8-byte halves of a row");
+    const int64_t base = i - lane;
+#ifdef RCBF_STUDY_EPW
+    const bool full_l = blockDim.x != 64 && (base + 64 <= B) && ((reinterpret_cast<uintptr_t>(obs) & 15) == 0);
+#else
+    const bool full_l = (base + 64 <= B) && ((reinterpret_cast<uintptr_t>(obs) & 15) == 0);
+#endif
+    // the same in every lane of the wave (base is the wave's first env), which the compiler cannot see: read
+    // from the first live lane it is a scalar, and the two paths a scalar branch instead of two lane masks
+    const bool full = __builtin_amdgcn_readfirstlane((int)full_l) != 0;
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NO / 2; ++k)
+            *reinterpret_cast<float2*>(&lds_wave[lane * NO + 2 * k]) = make_float2(o32[2 * k], o32[2 * k + 1]);
+    } else {
+        const OP ov = obs + i * NO;  // 40 B rows, 8 B aligned
+#pragma unroll
+        for (int k = 0; k < NO / 2; ++k) st_out2(ov + 2 * k, o32[2 * k], o32[2 * k + 1]);
+    }
+    return full;
+}
+
 // One fused safe step of env i, from its state and inputs in registers (xs, a,
 // st, us, m, s; ep_pre / ep0: the episode counter loaded ahead, see
 // reset_foreseeable) to every store a step makes: the state pairs, aux, step,
@@ -192,7 +264,7 @@ __device__ __forceinline__ void store_obs32_staged(OP obs, int64_t i, int64_t B,
 // instruction by type; k_safe_step passes its kernel arguments as they are.  OBS_SC1: the staged observation
 // chunks' store flavour (st_out4); OBS_PLAIN: plain stores instead (k_safe_steps_traj's study switch).
 template <int SOLVER, int MODE, int K, bool ST, bool WT, bool GP = false,
-          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, bool OBS_PLAIN = false>
+          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, bool OBS_PLAIN = false, int CARRY = 0>
 __device__ __forceinline__ void safe_step_body(
     const rcbf_params& prm, int64_t B, int64_t i, ptr_g<GP, double> __restrict__ x, ptr_g<GP, double> __restrict__ aux,
     ptr_g<GP, int32_t> __restrict__ step, ptr_g<GP, uint32_t> __restrict__ episode,
@@ -201,8 +273,12 @@ __device__ __forceinline__ void safe_step_body(
     ptr_g<GP, int32_t> __restrict__ status_out, ptr_g<GP, int32_t> fail_flag, int auto_reset,
     uint64_t seed, int64_t off, double* xs, double& a, int& st, const float* us, const float* m, const float* s,
     bool ep_pre, uint32_t ep0, const Stamps<ST>& stamps, float* obs_stage, char* wt_lds, int lane,
-    bool* did_reset = nullptr) {
+    bool* did_reset = nullptr, float* obs_c = nullptr, float (*G_c)[Dims<MODE, K>::N] = nullptr,
+    float* h_c = nullptr, const float* u_nx = nullptr) {
     using D = Dims<MODE, K>;
+    static_assert(CARRY == 0 || (MODE == RCBF_MODE_SIMULATED_CARS && RCBF_EARLY_STORE && !ST && !WT && GP &&
+                                 SOLVER == RCBF_SOLVER_ACTIVE_SET && RCBF_FUSED_RAW_ROWS != 0),
+                  "the carried observation: the cars fused loop only");
     const int64_t wbase = i - lane;
     const bool wfull = wbase + 64 <= B;  // wave-uniform: every lane of this wave is live
     constexpr int kWtBytes = WT ? 16 * 160 : 16;  // the caller's per-wave wt_lds block
@@ -223,13 +299,29 @@ __device__ __forceinline__ void safe_step_body(
         // first; the layer's chain (state32 -> rows -> QP -> clamp) then
         // finishes car 3's velocity (pair 3) and the observation.
         float s32[D::NS];
-        state_from_env<MODE>(xs, s32);  // the layer reads the pre-step state
+        if constexpr (CARRY == 0) state_from_env<MODE>(xs, s32);  // the layer reads the pre-step state
+        if constexpr (CARRY == 1) state_from_obs32<MODE>(obs_c, s32);  // ... through the row the last step stored
         // the exact solver on the raw rows: the rows are built here, ahead of
         // the env's pre-step part, whose arithmetic can then fill their latency
         // (3.69 -> 3.65 us per step, profiles/r03/rows_first_ab_r03q.txt)
         constexpr bool kRowsFirst = SOLVER == RCBF_SOLVER_ACTIVE_SET && RCBF_FUSED_RAW_ROWS != 0;
         LayerState<MODE, K> L;
-        if constexpr (kRowsFirst) diff_rows<MODE, K>(prm, s32, us, m, s, L.G, L.h, nullptr);
+        if constexpr (CARRY == 2) {
+            // ... and the rows themselves were built in the last step's tail
+#pragma unroll
+            for (int r = 0; r < D::M; ++r) {
+                L.h[r] = h_c[r];
+#pragma unroll
+                for (int k = 0; k < D::N; ++k) L.G[r][k] = G_c[r][k];
+            }
+        } else if constexpr (kRowsFirst) {
+            diff_rows<MODE, K>(prm, s32, us, m, s, L.G, L.h, nullptr);
+        }
+        constexpr bool kSolveFirst = CARRY == 2 && RCBF_FUSED_CARRY_SOLVE_FIRST != 0;
+        if constexpr (kSolveFirst) {
+            layer_solve_raw<MODE, K>(prm, us, uf, L);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         CarsStepOut o;
         const double acc3 = cars_env_pre(prm, xs, a, st, o);
         dn = o.done;
@@ -259,7 +351,9 @@ __device__ __forceinline__ void safe_step_body(
             st_out(&step[i], st);
         }
         __builtin_amdgcn_sched_barrier(0);  // keep the early stores ahead of the layer's chain
-        if constexpr (kRowsFirst) {
+        if constexpr (kSolveFirst) {
+            // solved above
+        } else if constexpr (kRowsFirst) {
             layer_solve_raw<MODE, K>(prm, us, uf, L);  // the same solve as layer_forward<..., RAW>
         } else {
             layer_forward<SOLVER, MODE, K, false, false, RCBF_FUSED_RAW_ROWS != 0>(prm, s32, us, m, s, uf, L);
@@ -283,7 +377,29 @@ __device__ __forceinline__ void safe_step_body(
             st_out(&step[i], st);
         }
     }
-    store_obs32_staged<MODE, WT, OBS_SC1, ptr_g<GP, float>, OBS_PLAIN>(obs_out, i, B, xs, oc, obs_stage, lane);
+    bool obs_staged = false;
+    if constexpr (CARRY != 0) {
+        // The observation of the post-step (or reset) state, computed once: the row stored here is the row the
+        // next step's layer reads (obs_c).  A full wave's rows go to LDS now and leave as chunks at the end of
+        // the step; behind the LDS writes come the next step's state32 and rows (CARRY == 2: from obs_c, the
+        // priors and the next action, all in registers) and this step's u, reward, cost and done stores.
+        double o[D::NO];
+        env_obs<MODE>(xs, o);
+#pragma unroll
+        for (int k = 0; k < D::NO; ++k) obs_c[k] = (float)o[k];
+        obs_staged = stage_obs32_row<MODE>(obs_out, i, B, obs_c, obs_stage, lane);
+        if constexpr (CARRY == 2) {
+            float s32n[D::NS];
+            state_from_obs32<MODE>(obs_c, s32n);
+            diff_rows<MODE, K>(prm, s32n, u_nx, m, s, G_c, h_c, nullptr);
+            // the rows are finished here, behind the LDS writes and ahead of the stores below (nothing is emitted;
+            // the compiler otherwise moves their arithmetic behind the chunk stores, to where the next step
+            // reads them); the other entries of G are constants
+            asm volatile("" : "+v"(G_c[0][0]), "+v"(G_c[1][0]), "+v"(h_c[0]), "+v"(h_c[1]), "+v"(h_c[2]), "+v"(h_c[3]));
+        }
+    } else {
+        store_obs32_staged<MODE, WT, OBS_SC1, ptr_g<GP, float>, OBS_PLAIN>(obs_out, i, B, xs, oc, obs_stage, lane);
+    }
     if constexpr (WT) {
         constexpr int NU4 = 4 * D::NU;
         float ufc[D::NU];
@@ -334,6 +450,10 @@ __device__ __forceinline__ void safe_step_body(
         st_out(&cost[i], cst);
         st_out(&done[i], (uint8_t)dn);
         if (goal_met) st_out(&goal_met[i], (uint8_t)gm);
+    }
+    if constexpr (CARRY != 0) {
+        if (obs_staged)
+            store_obs_chunks<MODE, WT, OBS_SC1, ptr_g<GP, float>, OBS_PLAIN, true>(obs_out, wbase, obs_stage, lane);
     }
     if (did_reset) *did_reset = auto_reset && dn;  // the condition under which the step above reset the env
     stamps.mark(6, false);
@@ -461,6 +581,11 @@ __global__ void __launch_bounds__(BS) k_safe_step(int64_t B, double* __restrict_
 // registers (256-thread workgroups).
 // TRAJ (k_safe_steps_traj): no kernel is plain.  With the recorded outputs' pointers changing every step the
 // cars kernel and the unicycle at k = 1, written plain, spill 5 and 2 scalar registers (64-thread workgroups).
+template <int MODE>
+constexpr int fused_carry() {
+    return MODE == RCBF_MODE_SIMULATED_CARS ? RCBF_FUSED_CARRY : 0;
+}
+
 template <int MODE, int K, bool TRAJ = false>
 constexpr bool fused_plain() {
     return !TRAJ && (MODE == RCBF_MODE_SIMULATED_CARS || K == 1);

@@ -114,9 +114,33 @@
     // alone).  A wait for one of these loads inside the loop would be passed again in every step, where all
     // it can wait for is the last step's stores.
     __builtin_amdgcn_s_waitcnt(0x0f70);
+    // Cars: what the loop carries from one step's tail to the next step's head (fused_carry, rcbf_safe_step.hpp).
+    // obs_c: the fp32 observation row of env i's current state, which a step's layer reads through get_state
+    // and which the step before it has just computed for its obs store; Gc, hc (the study form only): the
+    // layer's raw rows for that state and the next action, built in that tail.  Derived here once from the
+    // state just loaded, exactly as a step derives them (state_from_env, diff_rows), so a dispatch starts from
+    // HBM alone.
+    constexpr int CARRY = fused_carry<MODE>();
+    float obs_c[D::NO], Gc[D::M][D::N], hc[D::M];
+    if constexpr (CARRY != 0) {
+        double o[D::NO];
+        env_obs<MODE>(xs, o);
+#pragma unroll
+        for (int k = 0; k < D::NO; ++k) obs_c[k] = (float)o[k];
+        if constexpr (CARRY == 2) {
+            float s32[D::NS];
+            state_from_obs32<MODE>(obs_c, s32);
+            diff_rows<MODE, K>(prm, s32, us, m, s, Gc, hc, nullptr);
+        }
+    }
 #pragma nounroll
     while (leftv > 0) {
         RCBF_OPAQUE_V();  // every step: nothing derived from them is loop-invariant to the compiler
+        // The plain cars loop has no scalar register to spare (with the rows carried too, RCBF_FUSED_CARRY == 2,
+        // it spilled four): the two pointers that only a reset and a failed solve use, as per-lane values (no
+        // instruction).  Their null tests and env i's addresses are then worked out where those rare paths
+        // need them, instead of standing in scalar registers over the whole step.
+        if constexpr (PLAIN && CARRY != 0) asm volatile("" : "+v"(epv), "+v"(failv));
         const rcbf_params* prm_p = &prm;
         if constexpr (!PLAIN) {
 #pragma unroll
@@ -166,9 +190,10 @@
         }
         bool rs = false;
         constexpr bool OBS_PLAIN = TRAJ && RCBF_TRAJ_OBS_PLAIN != 0;  // study switch (rcbf_safe_step.hpp)
-        safe_step_body<SOLVER, MODE, K, false, WT, true, OBS_SC1, OBS_PLAIN>(
+        safe_step_body<SOLVER, MODE, K, false, WT, true, OBS_SC1, OBS_PLAIN, CARRY>(
             prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv, costv, donev, goalv, statv, failv, arv, seedv, offv, xs,
-            a, st, us, m, s, epv != nullptr, epr, stamps, obs_stage[widv], nullptr, lanev, &rs);
+            a, st, us, m, s, epv != nullptr, epr, stamps, obs_stage[widv], nullptr, lanev, &rs, CARRY ? obs_c : nullptr, CARRY ? Gc : nullptr, CARRY ? hc : nullptr,
+            CARRY ? un : nullptr);
         epr += rs ? 1u : 0u;  // a reset stored epr + 1
         // this step's chunk reads of obs_stage stay ahead of the next step's writes to it (one wave's LDS
         // operations execute in order; this keeps the compiler from reordering them)

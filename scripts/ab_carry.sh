@@ -1,0 +1,43 @@
+# A/B of the cars fused loop's carried observation and prebuilt rows (fused_carry, csrc/rcbf_safe_step.hpp)
+# against the commit before it, in one GPU session, the libraries alternating, 5 rounds: this tree ("new")
+# against a built checkout of the parent commit ("old"), and, where they were built, the study variants
+# build/variants/librcbf_NAME.co (python __graft_entry__.py variant NAME -DRCBF_FUSED_CARRY=..), which run on
+# this tree's library with their own step kernels.  Legs (scripts/exp_traj_ab.py, B = 65 536, 20 and 1 000
+# steps; one JSON line per figure in OUT/TAG/LIB_ENV.jsonl): cars, the plain fused plan and the trajectory
+# plan; the unicycle at k = 5, the plain fused plan, as the control (its kernels did not change).  Then
+# bench.py's driver form and its default form with --dump-outputs from both trees, compared bit for bit.
+# Usage: [RCBF_AB_OUT=OUT] [RCBF_AB_VARIANTS="NAME .."] bash scripts/ab_carry.sh TAG [PARENT_TREE]
+cd "$(dirname "$0")/.."; R=$PWD; O=${RCBF_AB_OUT:-bench_out}; case $O in /*) ;; *) O=$R/$O;; esac; O=$O/$1
+P=${2:-build/parent_tree}; mkdir -p $O
+V=$P/sac-rcbf_amd/rcbf_amd/librcbf_hip.so
+[ -f $V ] || { echo "no parent build at $V"; exit 1; }
+for n in $RCBF_AB_VARIANTS; do [ -f build/variants/librcbf_$n.co ] || { echo "no variant $n"; exit 1; }; done
+for r in 1 2 3 4 5; do
+  for w in cars u5; do
+    f=fused; [ $w = cars ] && f=traj,fused
+    timeout -k 10 150 python scripts/exp_traj_ab.py --env $w --forms $f >> $O/new_$w.jsonl 2>> $O/err.log || exit 1
+    RCBF_HIP_LIB=$V timeout -k 10 150 python scripts/exp_traj_ab.py --env $w --forms $f --lib-tag old \
+      >> $O/old_$w.jsonl 2>> $O/err.log || exit 1
+  done
+  for n in $RCBF_AB_VARIANTS; do
+    timeout -k 10 150 python scripts/exp_traj_ab.py --env cars --forms traj,fused --lib-tag $n \
+      --code-object build/variants/librcbf_$n.co >> $O/${n}_cars.jsonl 2>> $O/err.log || exit 1
+  done
+done
+for form in driver default; do
+  a=""; [ $form = driver ] && a="--gpus 1 --steps 20 --warmup 5"
+  timeout -k 10 300 python bench.py $a --dump-outputs $O/dump_${form}_new > $O/bench_${form}_new.log 2>&1 || exit 1
+  (cd $P && timeout -k 10 300 python bench.py $a --dump-outputs $O/dump_${form}_old > $O/bench_${form}_old.log 2>&1) || exit 1
+  python scripts/exp_traj_ab.py --compare-dumps $O/dump_${form}_new $O/dump_${form}_old | tee $O/dump_compare_$form.txt || exit 1
+done
+python - $O <<'EOF'
+import glob, json, os, sys
+rows = {}
+for p in sorted(glob.glob(os.path.join(sys.argv[1], "*.jsonl"))):
+    for ln in open(p):
+        r = json.loads(ln)
+        rows.setdefault((r["env"], r["form"], r["K"], r["lib"]), []).append(r["us_per_step_median"])
+for k in sorted(rows):
+    v = sorted(rows[k])
+    print("%-5s %-6s K=%-5d %-8s medians %s  median %.4f  min-max %.4f-%.4f" % (*k, v, v[len(v) // 2], v[0], v[-1]))
+EOF
