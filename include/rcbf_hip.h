@@ -370,6 +370,31 @@ int rcbf_state_from_obs(const rcbf_params* prm, int64_t B, const float* obs, flo
 int rcbf_ring_scatter_f64(double* ring, int64_t cap, int64_t W, int64_t pos,
                           const double* src, int64_t n, hipStream_t stream);
 
+/* The K x B transitions of a trajectory plan (rcbf_aql_safe_step_term_plan)
+ * as packed ReplayMemory records in the ring, one launch, no intermediate
+ * array.  Replaces the warm-up loop's memory.push per step (main.py:100-107).
+ * Transition r = j B + i (step-major: the order B envs stepped in lock-step
+ * push in) is the record [obs_prev | action | reward | next_obs | mask | t |
+ * next_t] of W = 2 n_o + n_u + 4 doubles at slot (position + r) mod capacity;
+ * if K B > capacity the first K B - capacity transitions are not written (the
+ * state sequential pushes leave).  obs0 (B, n_o) f32: the observation step 0
+ * acted on; step0 (B,) i32: each env's step counter before the plan; obs,
+ * term_obs [nullable], u: (K, P, w) f32 with pitch P >= B envs; reward (K, P)
+ * f32; done (K, P) u8.
+ *   obs_prev = obs0[i] for j = 0, else obs[j-1][i]
+ *   next_obs = term_obs[j][i] if done[j][i] and auto_reset and term_obs, else obs[j][i]
+ *   with c = step0[i] before step 0, per step: e = c + 1;
+ *   mask = 1 if e == max_episode_steps else 1 - done (main.py:105);
+ *   t = (double)e * dt; next_t = (double)(e + 1) * dt;
+ *   then c = (done and auto_reset) ? 0 : e
+ * fp32 widens exactly, so the ring is bit-reproducible from the inputs.
+ * (n_o, n_u) = (10, 1) or (7, 2); cars rows (n_o = 10) are read as 8-byte
+ * pairs: obs0, obs and term_obs 8-byte aligned (RCBF_E_BAD_SHAPE). */
+int rcbf_traj_pack_replay_f64(double* ring, int64_t capacity, int64_t position, int64_t B, int32_t K, int64_t P,
+                              int32_t n_o, int32_t n_u, const float* obs0, const int32_t* step0, const float* obs,
+                              const float* term_obs, const float* u, const float* reward, const uint8_t* done,
+                              int32_t max_episode_steps, double dt, int32_t auto_reset, hipStream_t stream);
+
 /* ReplayMemory.sample (replay_memory.py:31-35) gather: dst[r] = ring[idx[r]]. */
 int rcbf_gather_rows_f64(double* dst, const double* ring, int64_t W, const int64_t* idx,
                          int64_t n, hipStream_t stream);
@@ -592,7 +617,32 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
  * the whole (K, P, w) extent of every recorded output); otherwise PER STEP: K
  * dispatches of k_safe_step, step j's argument block pointing each recorded
  * output at row j.  The queries, rcbf_aql_run and rcbf_aql_plan_free work on
- * these plans unchanged. */
+ * these plans unchanged.
+ *
+ * rcbf_aql_safe_step_term_plan: rcbf_aql_safe_step_traj_plan that can also
+ * keep the TERMINAL observation of every episode the plan ends, which a step
+ * that auto-resets otherwise never stores (its obs row is the next episode's
+ * first).  The arguments of rcbf_aql_safe_step_traj_plan, then term_obs.
+ *   - traj_mask with RCBF_TRAJ_TERM_OBS: term_obs is the base of a dense
+ *     (K, P, n_o) fp32 array, P = traj_pitch, 16-byte aligned like a recorded
+ *     obs (RCBF_E_BAD_SHAPE otherwise).  On a step j that resets env i
+ *     (auto_reset and done) the kernel writes at [j][i] the observation of
+ *     env i's post-step state before the reset: bit for bit the row
+ *     rcbf_safe_step with auto_reset = 0 stores from the same pre-step state
+ *     and action.  No other element is ever written (steps without a reset,
+ *     columns [B, P), rows >= K, everything when auto_reset = 0).  Every
+ *     other output is that of the trajectory plan with the same mask.
+ *   - The bit with a NULL term_obs, or term_obs with the bit clear:
+ *     RCBF_E_BAD_MODE.  Without the bit and the pointer this is
+ *     rcbf_aql_safe_step_traj_plan.
+ *   - Such a plan is always FUSED, K = 1 included (one dispatch of
+ *     k_safe_steps_term, from librcbf_steps_term.co, per chunk of at most
+ *     4096 steps).  Whatever keeps another plan in the per-step form is
+ *     RCBF_E_BAD_MODE here: a solver other than the exact active set,
+ *     span_out, RCBF_AQL_PROFILE, RCBF_AQL_STUDY_*, RCBF_AQL_PER_STEP, a u_RL
+ *     buffer that overlaps a written buffer (term_obs's whole (K, P, n_o)
+ *     extent included), a queue opened without librcbf_steps_term.co.
+ *     RCBF_AQL_PROFILE_ENDS works. */
 #define RCBF_TRAJ_OBS 1
 #define RCBF_TRAJ_U 2
 #define RCBF_TRAJ_REWARD 4
@@ -600,6 +650,7 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
 #define RCBF_TRAJ_DONE 16
 #define RCBF_TRAJ_GOAL_MET 32
 #define RCBF_TRAJ_STATUS 64
+#define RCBF_TRAJ_TERM_OBS 128 /* rcbf_aql_safe_step_term_plan only: the pre-reset observation, see there */
 #define RCBF_AQL_PROFILE 1
 /* plan flags: memory-fence scopes (default: agent scope everywhere but the
  * last packet's release, which is system scope) */
@@ -613,6 +664,7 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
 #define RCBF_AQL_SAFE_STEP_KERNARG_BYTES 408 /* sizeof the k_safe_step argument block */
 #define RCBF_AQL_SAFE_STEPS_KERNARG_BYTES 408 /* sizeof the k_safe_steps (fused form) argument block */
 #define RCBF_AQL_SAFE_STEPS_TRAJ_KERNARG_BYTES 424 /* ... of k_safe_steps_traj: + traj_mask (408), traj_pitch (416) */
+#define RCBF_AQL_SAFE_STEPS_TERM_KERNARG_BYTES 432 /* ... of k_safe_steps_term: + term_obs (424) */
 typedef struct rcbf_aql rcbf_aql;
 typedef struct rcbf_aql_plan rcbf_aql_plan;
 int rcbf_aql_open(int32_t device, const char* code_object, int32_t flags, rcbf_aql** out);
@@ -631,6 +683,13 @@ int rcbf_aql_safe_step_traj_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B,
                                  int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
                                  int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
                                  int64_t traj_pitch, rcbf_aql_plan** out);
+int rcbf_aql_safe_step_term_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                                 int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
+                                 const float* mu, const float* sigma, int32_t prior_cols, float* obs_out,
+                                 float* u_out, float* reward, float* cost, uint8_t* done, uint8_t* goal_met,
+                                 int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
+                                 int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
+                                 int64_t traj_pitch, float* term_obs, rcbf_aql_plan** out);
 int rcbf_aql_run(rcbf_aql_plan* plan, uint64_t timeout_us);
 int rcbf_aql_plan_times(const rcbf_aql_plan* plan, uint64_t* start_end_ns);
 int rcbf_aql_plan_dispatches(const rcbf_aql_plan* plan);

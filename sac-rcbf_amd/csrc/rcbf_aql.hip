@@ -105,6 +105,8 @@ static_assert(sizeof(SafeStepArgs) == RCBF_AQL_SAFE_STEP_KERNARG_BYTES, "kernarg
 static_assert(sizeof(SafeStepsArgs) == RCBF_AQL_SAFE_STEPS_KERNARG_BYTES, "kernarg layout");
 // ... and its trajectory form (rcbf::k_safe_steps_traj) rcbf::SafeStepsTrajArgs
 static_assert(sizeof(SafeStepsTrajArgs) == RCBF_AQL_SAFE_STEPS_TRAJ_KERNARG_BYTES, "kernarg layout");
+// ... and the form that keeps the terminal observation (rcbf::k_safe_steps_term) rcbf::SafeStepsTermArgs
+static_assert(sizeof(SafeStepsTermArgs) == RCBF_AQL_SAFE_STEPS_TERM_KERNARG_BYTES, "kernarg layout");
 
 struct KernelInfo {
     std::string name;  // mangled symbol without ".kd"
@@ -113,8 +115,8 @@ struct KernelInfo {
 };
 
 constexpr uint32_t kQueueSize = 4096;  // packets (power of two); a plan longer than this is fed in chunks
-constexpr size_t kArgStride = 512;     // bytes per step's kernarg block (>= 424, 64-B multiple)
-static_assert(sizeof(SafeStepsTrajArgs) <= kArgStride, "kernarg block");
+constexpr size_t kArgStride = 512;     // bytes per step's kernarg block (>= 432, 64-B multiple)
+static_assert(sizeof(SafeStepsTermArgs) <= kArgStride, "kernarg block");
 constexpr int32_t kTrajAll = RCBF_TRAJ_OBS | RCBF_TRAJ_U | RCBF_TRAJ_REWARD | RCBF_TRAJ_COST | RCBF_TRAJ_DONE |
                              RCBF_TRAJ_GOAL_MET | RCBF_TRAJ_STATUS;
 constexpr int32_t kFusedChunk = (int32_t)kQueueSize;  // most steps one fused dispatch runs: a bounded kernel
@@ -135,13 +137,17 @@ struct rcbf_aql {
     hsa_code_object_reader_t reader_traj{};  // librcbf_steps_traj.co (the k_safe_steps_traj kernels), if there
     hsa_executable_t exe{};
     hsa_executable_t exe_traj{};  // its own executable: no symbol of one code object can meet one of the other
+    hsa_code_object_reader_t reader_term{};  // librcbf_steps_term.co (the k_safe_steps_term kernels), if there
+    hsa_executable_t exe_term{};
     bool have_reader = false, have_reader_traj = false, have_exe = false, have_exe_traj = false, hsa_up = false;
-    std::vector<char> code, code_traj;
+    bool have_reader_term = false, have_exe_term = false;
+    std::vector<char> code, code_traj, code_term;
     std::vector<KernelInfo> kernels;
     std::atomic<int> queue_error{0};
     int profiling = 0;
     bool fused = false;  // the code object has the k_safe_steps kernels (the fused plan form)
     bool traj = false;   // ... and the k_safe_steps_traj kernels (the fused form of a trajectory plan)
+    bool term = false;   // ... and the k_safe_steps_term kernels (trajectory plans with RCBF_TRAJ_TERM_OBS)
 };
 
 struct rcbf_aql_plan {
@@ -232,6 +238,29 @@ std::string safe_steps_traj_prefix(int mode, int k, int bs) {
     return buf;
 }
 
+// ... and of rcbf::k_safe_steps_term<MODE, K, BS> (SafeStepsTermArgs)
+std::string safe_steps_term_prefix(int mode, int k, int bs) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "_ZN4rcbf17k_safe_steps_termILi%dELi%dELi%dEEEv", mode, k, bs);
+    return buf;
+}
+
+// The optional code object NAME<suffix>.co beside NAME.co, read whole into `code` (left empty when the file is
+// not there).  false: there, but unreadable -- an error, not a quiet fall back.
+bool read_side_code_object(const std::string& path, const char* suffix, std::vector<char>& code) {
+    if (path.size() <= 3 || path.compare(path.size() - 3, 3, ".co") != 0) return true;
+    const std::string tpath = path.substr(0, path.size() - 3) + suffix + ".co";
+    FILE* tf = fopen(tpath.c_str(), "rb");
+    if (!tf) return true;
+    fseek(tf, 0, SEEK_END);
+    const long tn = ftell(tf);
+    fseek(tf, 0, SEEK_SET);
+    code.resize(tn > 0 ? (size_t)tn : 0);
+    const bool ok = tn > 0 && fread(code.data(), 1, (size_t)tn, tf) == (size_t)tn;
+    fclose(tf);
+    return ok;
+}
+
 // p moved on by `rows` rows of `row_bytes` bytes (64-bit arithmetic); a null pointer stays null
 template <typename T>
 T* rows_on(T* p, int64_t rows, int64_t row_bytes) {
@@ -272,8 +301,10 @@ void destroy(rcbf_aql* q) {
     if (q->queue) hsa_queue_destroy(q->queue);
     if (q->have_exe) hsa_executable_destroy(q->exe);
     if (q->have_exe_traj) hsa_executable_destroy(q->exe_traj);
+    if (q->have_exe_term) hsa_executable_destroy(q->exe_term);
     if (q->have_reader) hsa_code_object_reader_destroy(q->reader);
     if (q->have_reader_traj) hsa_code_object_reader_destroy(q->reader_traj);
+    if (q->have_reader_term) hsa_code_object_reader_destroy(q->reader_term);
     if (q->hsa_up) hsa_shut_down();
     delete q;
 }
@@ -314,20 +345,15 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     }
     // the trajectory plans' kernels: NAME_traj.co beside NAME.co.  Without it the queue opens as before and
     // trajectory plans take the per-step form.
-    if (path.size() > 3 && path.compare(path.size() - 3, 3, ".co") == 0) {
-        const std::string tpath = path.substr(0, path.size() - 3) + "_traj.co";
-        if (FILE* tf = fopen(tpath.c_str(), "rb")) {
-            fseek(tf, 0, SEEK_END);
-            const long tn = ftell(tf);
-            fseek(tf, 0, SEEK_SET);
-            q->code_traj.resize(tn > 0 ? (size_t)tn : 0);
-            const bool ok = tn > 0 && fread(q->code_traj.data(), 1, (size_t)tn, tf) == (size_t)tn;
-            fclose(tf);
-            if (!ok) {  // there, but unreadable: an error, not a quiet fall back
-                delete q;
-                return RCBF_E_BAD_SHAPE;
-            }
-        }
+    if (!read_side_code_object(path, "_traj", q->code_traj)) {
+        delete q;
+        return RCBF_E_BAD_SHAPE;
+    }
+    // ... and NAME_term.co, the kernels of the plans that keep the terminal observation: without it those
+    // plans are refused (they have no per-step form) and everything else works as before
+    if (!read_side_code_object(path, "_term", q->code_term)) {
+        delete q;
+        return RCBF_E_BAD_SHAPE;
     }
     int rc = hsa_rc(hsa_init());
     if (rc) {
@@ -372,11 +398,25 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
         if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_traj, nullptr));
         if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_traj, q->agent, collect_kernel, q));
     }
+    if (!rc && !q->code_term.empty()) {
+        rc = hsa_rc(
+            hsa_code_object_reader_create_from_memory(q->code_term.data(), q->code_term.size(), &q->reader_term));
+        if (!rc) q->have_reader_term = true;
+        if (!rc)
+            rc = hsa_rc(hsa_executable_create_alt(HSA_PROFILE_FULL, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr,
+                                                  &q->exe_term));
+        if (!rc) q->have_exe_term = true;
+        if (!rc)
+            rc = hsa_rc(
+                hsa_executable_load_agent_code_object(q->exe_term, q->agent, q->reader_term, nullptr, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_term, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_term, q->agent, collect_kernel, q));
+    }
     // every k_safe_step instantiation in the code object must take exactly the
     // argument block SafeStepArgs describes
     // ... and every k_safe_steps instantiation SafeStepsArgs; a code object without them still opens, and
     // its plans take the per-step form; likewise k_safe_steps_traj and SafeStepsTrajArgs
-    int n_steps = 0, n_fused = 0, n_traj = 0;
+    int n_steps = 0, n_fused = 0, n_traj = 0, n_term = 0;
     for (const auto& k : q->kernels) {
         if (k.name.compare(0, 21, "_ZN4rcbf11k_safe_step") == 0) {
             ++n_steps;
@@ -387,11 +427,15 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
         } else if (k.name.compare(0, 27, "_ZN4rcbf17k_safe_steps_traj") == 0) {
             ++n_traj;
             if (k.kernarg_bytes != sizeof(SafeStepsTrajArgs) || k.private_bytes != 0) rc = RCBF_E_BAD_SHAPE;
+        } else if (k.name.compare(0, 27, "_ZN4rcbf17k_safe_steps_term") == 0) {
+            ++n_term;
+            if (k.kernarg_bytes != sizeof(SafeStepsTermArgs) || k.private_bytes != 0) rc = RCBF_E_BAD_SHAPE;
         }
     }
     if (!rc && n_steps == 0) rc = RCBF_E_BAD_MODE;
     q->fused = n_fused > 0;
     q->traj = n_traj > 0;
+    q->term = n_term > 0;
     if (!rc)
         rc = hsa_rc(hsa_queue_create(q->agent, kQueueSize, HSA_QUEUE_TYPE_SINGLE, queue_error_cb, q, UINT32_MAX,
                                      UINT32_MAX, &q->queue));
@@ -411,14 +455,15 @@ int rcbf_aql_close(rcbf_aql* q) {
 
 int rcbf_aql_kernel_count(const rcbf_aql* q) { return q ? (int)q->kernels.size() : RCBF_E_NULL; }
 
-// rcbf_aql_safe_step_plan (traj_mask = 0) and rcbf_aql_safe_step_traj_plan
+// rcbf_aql_safe_step_plan (traj_mask = 0), rcbf_aql_safe_step_traj_plan (term_obs = nullptr) and
+// rcbf_aql_safe_step_term_plan
 static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
                                 int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
                                 const float* mu, const float* sigma, int32_t prior_cols, float* obs_out,
                                 float* u_out, float* reward, float* cost, uint8_t* done, uint8_t* goal_met,
                                 int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
                                 int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
-                                int64_t traj_pitch, rcbf_aql_plan** out) {
+                                int64_t traj_pitch, float* term_obs, rcbf_aql_plan** out) {
     if (!q || !out) return RCBF_E_NULL;
     *out = nullptr;
     if (int e = check_prm(prm)) return e;
@@ -432,13 +477,17 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
     if (span_out && (((uintptr_t)span_out) & 15)) return RCBF_E_BAD_SHAPE;
     if (span_out && prm->solver != RCBF_SOLVER_ACTIVE_SET) return RCBF_E_BAD_MODE;
     // the trajectory contract (rcbf_hip.h)
-    if (traj_mask & ~kTrajAll) return RCBF_E_BAD_MODE;
+    // RCBF_TRAJ_TERM_OBS and its pointer come together (rcbf_aql_safe_step_term_plan) or not at all
+    const bool term = (traj_mask & RCBF_TRAJ_TERM_OBS) != 0;
+    if (term != (term_obs != nullptr)) return RCBF_E_BAD_MODE;
+    if (traj_mask & ~(kTrajAll | RCBF_TRAJ_TERM_OBS)) return RCBF_E_BAD_MODE;
     if (traj_mask && span_out) return RCBF_E_BAD_MODE;
     if (!goal_met) traj_mask &= ~RCBF_TRAJ_GOAL_MET;  // a null pointer is not recorded, and never advanced
     if (!status_out) traj_mask &= ~RCBF_TRAJ_STATUS;
     if (!traj_mask) traj_pitch = 0;
     if (traj_mask && (traj_pitch < B || traj_pitch % 4 != 0)) return RCBF_E_BAD_SHAPE;
     if ((traj_mask & RCBF_TRAJ_OBS) && (((uintptr_t)obs_out) & 15)) return RCBF_E_BAD_SHAPE;
+    if (term && (((uintptr_t)term_obs) & 15)) return RCBF_E_BAD_SHAPE;
     // RCBF_AQL_PROFILE: a completion signal (timestamps) on every packet; RCBF_AQL_PROFILE_ENDS: on the first
     // and the last only, so the run is timed end to end without a signal between steps (each one adds
     // ~1.5 us to its step: profiles/r06/aql_dispatch_signal_cost)
@@ -476,11 +525,17 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
     const int64_t row_done = traj_mask & RCBF_TRAJ_DONE ? P : 0;
     const int64_t row_goal = traj_mask & RCBF_TRAJ_GOAL_MET ? P : 0;
     const int64_t row_stat = traj_mask & RCBF_TRAJ_STATUS ? P * 4 : 0;
+    const int64_t row_term = term ? P * (int64_t)no * 4 : 0;
     const KernelInfo* kf = nullptr;
-    if (q->fused && K > 1 && solver == RCBF_SOLVER_ACTIVE_SET && !span_out && !(flags & kPerStepFlags))
-        kf = traj_mask ? (q->traj ? find_kernel(q, safe_steps_traj_prefix(mode, k, bs)) : nullptr)
-                       : find_kernel(q, safe_steps_prefix(mode, k, bs));
-    if (kf && kf->kernarg_bytes != (traj_mask ? sizeof(SafeStepsTrajArgs) : sizeof(SafeStepsArgs))) kf = nullptr;
+    // a plan that keeps the terminal observation is fused at any K (k_safe_steps_term with steps = 1 included)
+    if (q->fused && (K > 1 || term) && solver == RCBF_SOLVER_ACTIVE_SET && !span_out && !(flags & kPerStepFlags))
+        kf = term        ? (q->term ? find_kernel(q, safe_steps_term_prefix(mode, k, bs)) : nullptr)
+             : traj_mask ? (q->traj ? find_kernel(q, safe_steps_traj_prefix(mode, k, bs)) : nullptr)
+                         : find_kernel(q, safe_steps_prefix(mode, k, bs));
+    if (kf && kf->kernarg_bytes != (term        ? sizeof(SafeStepsTermArgs)
+                                    : traj_mask ? sizeof(SafeStepsTrajArgs)
+                                                : sizeof(SafeStepsArgs)))
+        kf = nullptr;
     if (kf) {
         const size_t n = (size_t)B;
         // a recorded output: the whole (K, P, w) array
@@ -499,6 +554,7 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
                        {done, ext(row_done, n)},
                        {goal_met, ext(row_goal, n)},
                        {status_out, ext(row_stat, n * 4)},
+                       {term_obs, ext(row_term, 0)},
                        {fail_flag, 4}};
         for (int32_t j = 0; j < n_u_rl && kf; ++j)
             for (const auto& w : written)
@@ -507,6 +563,7 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
                     break;
                 }
     }
+    if (term && !kf) return RCBF_E_BAD_MODE;  // no per-step form keeps the terminal observation
     const int32_t npkt = kf ? (K + kFusedChunk - 1) / kFusedChunk : K;
 
     auto* p = new rcbf_aql_plan();
@@ -523,9 +580,11 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
         // the row the packet's first step writes of every recorded output: chunk j starts at step j kFusedChunk
         const int64_t r0 = kf ? (int64_t)j * kFusedChunk : (int64_t)j;
         if (kf) {
-            SafeStepsTrajArgs ta;
-            std::memset(&ta, 0, sizeof ta);
+            SafeStepsTermArgs ea;
+            std::memset(&ea, 0, sizeof ea);
+            SafeStepsTrajArgs& ta = ea.t;
             SafeStepsArgs& a = ta.s;
+            ea.term_obs = rows_on(term_obs, r0, row_term);
             ta.traj_mask = traj_mask;
             ta.traj_pitch = traj_pitch;
             a.B = B;
@@ -553,8 +612,9 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
             // chunk j: steps j kFusedChunk ... of the plan; its first step reads u_rl_seq[that index % n_u_rl]
             a.steps = std::min<int32_t>(kFusedChunk, K - j * kFusedChunk);
             a.ju0 = (int32_t)(((int64_t)j * kFusedChunk) % n_u_rl);
-            // k_safe_steps reads the first sizeof(SafeStepsArgs) bytes, k_safe_steps_traj all of it
-            std::memcpy(host.data() + (size_t)j * kArgStride, &ta, sizeof ta);
+            // k_safe_steps reads the first sizeof(SafeStepsArgs) bytes, k_safe_steps_traj the first
+            // sizeof(SafeStepsTrajArgs), k_safe_steps_term all of it
+            std::memcpy(host.data() + (size_t)j * kArgStride, &ea, sizeof ea);
             continue;
         }
         SafeStepArgs a;
@@ -644,7 +704,7 @@ int rcbf_aql_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int3
                             uint64_t* span_out, int32_t flags, rcbf_aql_plan** out) {
     return build_safe_step_plan(q, prm, B, K, x, aux, step, episode, u_rl_seq, n_u_rl, mu, sigma, prior_cols, obs_out,
                                 u_out, reward, cost, done, goal_met, status_out, fail_flag, auto_reset, seed,
-                                env_offset, span_out, flags, 0, 0, out);
+                                env_offset, span_out, flags, 0, 0, nullptr, out);
 }
 
 int rcbf_aql_safe_step_traj_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
@@ -656,7 +716,19 @@ int rcbf_aql_safe_step_traj_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B,
                                  int64_t traj_pitch, rcbf_aql_plan** out) {
     return build_safe_step_plan(q, prm, B, K, x, aux, step, episode, u_rl_seq, n_u_rl, mu, sigma, prior_cols, obs_out,
                                 u_out, reward, cost, done, goal_met, status_out, fail_flag, auto_reset, seed,
-                                env_offset, span_out, flags, traj_mask, traj_pitch, out);
+                                env_offset, span_out, flags, traj_mask, traj_pitch, nullptr, out);
+}
+
+int rcbf_aql_safe_step_term_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                                 int32_t* step, uint32_t* episode, const float* const* u_rl_seq, int32_t n_u_rl,
+                                 const float* mu, const float* sigma, int32_t prior_cols, float* obs_out,
+                                 float* u_out, float* reward, float* cost, uint8_t* done, uint8_t* goal_met,
+                                 int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
+                                 int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
+                                 int64_t traj_pitch, float* term_obs, rcbf_aql_plan** out) {
+    return build_safe_step_plan(q, prm, B, K, x, aux, step, episode, u_rl_seq, n_u_rl, mu, sigma, prior_cols, obs_out,
+                                u_out, reward, cost, done, goal_met, status_out, fail_flag, auto_reset, seed,
+                                env_offset, span_out, flags, traj_mask, traj_pitch, term_obs, out);
 }
 
 }  // extern "C"

@@ -314,6 +314,126 @@ __global__ void __launch_bounds__(256) k_gather_rows(double* __restrict__ dst, c
     dst[e] = ring[idx[r] * W + c];
 }
 
+// `n` doubles from this wave's LDS block (s) to ring[dst0 ...], one contiguous run, as whole 16-B lane vectors
+// wherever the destination allows it: a run that starts on an odd double (records are W doubles, W odd) stores
+// that one double alone, the aligned pairs follow (two 8-B LDS reads, one dwordx4 `nt` store, pair p by lane
+// p % 64), and an odd double left at the end leaves alone too.  Nothing of the ring is read.
+__device__ __forceinline__ void run_out(double* __restrict__ ring, int64_t dst0, const double* s, int n, int lane) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    if (n <= 0) return;
+    double* const p = ring + dst0;
+    const int head = (int)((reinterpret_cast<uintptr_t>(p) >> 3) & 1);
+    const int npair = (n - head) >> 1;
+    for (int q = lane; q < npair; q += 64) {
+        const d2 v = {s[head + 2 * q], s[head + 2 * q + 1]};
+        __builtin_nontemporal_store(v, reinterpret_cast<d2*>(p + head + 2 * q));
+    }
+    if (lane == 0 && head) __builtin_nontemporal_store(s[0], p);
+    if (lane == 1 && ((n - head) & 1)) __builtin_nontemporal_store(s[n - 1], p + n - 1);
+}
+
+// rcbf_traj_pack_replay_f64: the K x B transitions of a trajectory plan as packed replay records, written
+// straight into the ring.  One env per lane, a wave per workgroup; the lane that owns env i walks steps
+// [j0, j1) = blockIdx.y's chunk of `chunk` steps, carrying env i's episode-step count (recomputed from
+// step0 and the done bytes of the steps before j0: one byte per step, against ~300 of a transition) and the
+// row obs[j - 1][i], which is next_obs of one record and obs_prev of the next (loaded once).  Every input is
+// read once (`nt`); a wave's 64 rows of obs[j] are one contiguous block of memory.
+// Output: the wave's records of step j, r = j B + i, are consecutive slots of the ring, so its 64 W doubles
+// are ONE run of memory unless the ring wraps inside it (then two).  The lanes write their records to LDS
+// (a row per lane, W odd: no bank conflict), and the block leaves as 16-B lane vectors (run_out) instead of
+// W strided 8-B stores per lane.  Transitions r < skip (= K B - capacity when that is positive) are the
+// ones sequential pushes would have overwritten: not written, so no slot is written twice and at most
+// `cap` consecutive slots are written per wave and step -- one wrap at the most.
+template <int NO, int NU>
+__global__ void __launch_bounds__(64) k_traj_pack_replay(double* __restrict__ ring, int64_t cap, int64_t pos,
+                                                         int64_t skip, int64_t B, int K, int64_t P,
+                                                         const float* __restrict__ obs0,
+                                                         const int32_t* __restrict__ step0,
+                                                         const float* __restrict__ obs,
+                                                         const float* __restrict__ term,
+                                                         const float* __restrict__ u,
+                                                         const float* __restrict__ reward,
+                                                         const uint8_t* __restrict__ done, int max_steps, double dt,
+                                                         int auto_reset, int chunk) {
+    constexpr int W = 2 * NO + NU + 4;
+    __shared__ __attribute__((aligned(16))) double stage[64 * W];
+    const int lane = threadIdx.x;
+    const int64_t wbase = (int64_t)blockIdx.x * 64;
+    const int64_t i = wbase + lane;
+    const bool live = i < B;
+    const int nl = (int)(B - wbase < 64 ? B - wbase : 64);  // this wave's envs
+    const int j0 = (int)blockIdx.y * chunk;
+    const int j1 = j0 + chunk < K ? j0 + chunk : K;
+    // a row of NO floats: 8-byte pairs where rows are 8-byte aligned (cars, 40 B), dwords otherwise (28 B)
+    auto load_row = [](const float* __restrict__ row, float* o) {
+        if constexpr (NO % 2 == 0) {
+            typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+            for (int k = 0; k < NO / 2; ++k) {
+                const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(row) + k);
+                o[2 * k] = v.x;
+                o[2 * k + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NO; ++k) o[k] = ld_in(&row[k]);
+        }
+    };
+    int c = 0;
+    float prev[NO];
+#pragma unroll
+    for (int k = 0; k < NO; ++k) prev[k] = 0.0f;
+    if (live) {
+        c = ld_in(&step0[i]);
+        for (int j = 0; j < j0; ++j) {  // the count at the chunk's first step
+            const bool dn = ld_in(&done[(int64_t)j * P + i]) != 0;
+            c = (dn && auto_reset) ? 0 : c + 1;
+        }
+        load_row(j0 == 0 ? obs0 + i * NO : obs + ((int64_t)(j0 - 1) * P + i) * NO, prev);
+    }
+    for (int j = j0; j < j1; ++j) {
+        if (live) {
+            const int64_t e = (int64_t)j * P + i;
+            float cur[NO], nx[NO], uj[NU];
+            load_row(obs + e * NO, cur);
+#pragma unroll
+            for (int k = 0; k < NU; ++k) uj[k] = ld_in(&u[e * NU + k]);
+            const float rw = ld_in(&reward[e]);
+            const bool dn = ld_in(&done[e]) != 0;
+#pragma unroll
+            for (int k = 0; k < NO; ++k) nx[k] = cur[k];
+            if (dn && auto_reset && term) load_row(term + e * NO, nx);  // rare: the episode's last observation
+            const int ep = c + 1;
+            double* const rec = stage + lane * W;
+#pragma unroll
+            for (int k = 0; k < NO; ++k) rec[k] = (double)prev[k];
+#pragma unroll
+            for (int k = 0; k < NU; ++k) rec[NO + k] = (double)uj[k];
+            rec[NO + NU] = (double)rw;
+#pragma unroll
+            for (int k = 0; k < NO; ++k) rec[NO + NU + 1 + k] = (double)nx[k];
+            rec[2 * NO + NU + 1] = ep == max_steps ? 1.0 : 1.0 - (dn ? 1.0 : 0.0);
+            rec[2 * NO + NU + 2] = (double)ep * dt;
+            rec[2 * NO + NU + 3] = (double)(ep + 1) * dt;
+            c = (dn && auto_reset) ? 0 : ep;
+#pragma unroll
+            for (int k = 0; k < NO; ++k) prev[k] = cur[k];
+        }
+        __syncthreads();  // one wave: the records are in LDS
+        // the wave's kept records [qa, nl) of this step, at slots sa, sa + 1, ... (mod cap)
+        const int64_t r0 = (int64_t)j * B + wbase;
+        const int qa = skip > r0 ? (skip - r0 < nl ? (int)(skip - r0) : nl) : 0;
+        const int kept = nl - qa;
+        if (kept > 0) {
+            const int64_t sa = (pos + r0 + qa) % cap;
+            const int n1 = cap - sa < kept ? (int)(cap - sa) : kept;
+            run_out(ring, sa * W, stage + qa * W, n1 * W, lane);
+            run_out(ring, 0, stage + (qa + n1) * W, (kept - n1) * W, lane);
+        }
+        __syncthreads();  // ... and read, before the next step's records overwrite them
+    }
+}
+
 }  // namespace
 
 // DynamicsModel.get_state on fp32 observation rows (dynamics.py:190-232): the
@@ -392,6 +512,41 @@ int rcbf_ring_scatter_f64(double* ring, int64_t cap, int64_t W, int64_t pos, con
     if (!ring || !src) return RCBF_E_NULL;
     hipLaunchKernelGGL(k_ring_scatter, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, stream, ring, cap, W,
                        pos % cap, src, n);
+    return launch_status();
+}
+
+int rcbf_traj_pack_replay_f64(double* ring, int64_t capacity, int64_t position, int64_t B, int32_t K, int64_t P,
+                              int32_t n_o, int32_t n_u, const float* obs0, const int32_t* step0, const float* obs,
+                              const float* term_obs, const float* u, const float* reward, const uint8_t* done,
+                              int32_t max_episode_steps, double dt, int32_t auto_reset, hipStream_t stream) {
+    using DC = Dims<RCBF_MODE_SIMULATED_CARS, 1>;
+    using DU = Dims<RCBF_MODE_UNICYCLE, 1>;
+    const bool cars = n_o == DC::NO && n_u == DC::NU;
+    if (!cars && !(n_o == DU::NO && n_u == DU::NU)) return RCBF_E_BAD_SHAPE;
+    if (B < 0 || K <= 0 || P < B || capacity <= 0 || position < 0 || position >= capacity) return RCBF_E_BAD_SHAPE;
+    if (B == 0) return 0;
+    if (!ring || !obs0 || !step0 || !obs || !u || !reward || !done) return RCBF_E_NULL;
+    // cars rows are read as 8-byte pairs
+    if (cars && ((((uintptr_t)obs0) | ((uintptr_t)obs) | ((uintptr_t)term_obs)) & 7)) return RCBF_E_BAD_SHAPE;
+    if ((((uintptr_t)ring) & 7) || B > INT32_MAX) return RCBF_E_BAD_SHAPE;
+    const int64_t n = (int64_t)K * B;
+    const int64_t skip = n > capacity ? n - capacity : 0;
+    // steps per workgroup: the whole plan where the batch alone fills the chip (8 waves a CU), shorter chunks
+    // (each lane then first re-derives its step count from the done bytes before its chunk) where it does not
+    const int64_t waves = (B + 63) / 64, want = (int64_t)num_cus() * 8;
+    int64_t parts = waves >= want ? 1 : (want + waves - 1) / waves;
+    if (parts > K) parts = K;
+    if (parts > 65535) parts = 65535;
+    const int chunk = (int)((K + parts - 1) / parts);
+    const dim3 g((unsigned)waves, (unsigned)((K + chunk - 1) / chunk)), b(64);
+    if (cars)
+        hipLaunchKernelGGL((k_traj_pack_replay<DC::NO, DC::NU>), g, b, 0, stream, ring, capacity, position, skip, B,
+                           (int)K, P, obs0, step0, obs, term_obs, u, reward, done, (int)max_episode_steps, dt,
+                           (int)auto_reset, chunk);
+    else
+        hipLaunchKernelGGL((k_traj_pack_replay<DU::NO, DU::NU>), g, b, 0, stream, ring, capacity, position, skip, B,
+                           (int)K, P, obs0, step0, obs, term_obs, u, reward, done, (int)max_episode_steps, dt,
+                           (int)auto_reset, chunk);
     return launch_status();
 }
 

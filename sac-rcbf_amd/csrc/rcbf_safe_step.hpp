@@ -263,8 +263,14 @@ __device__ __forceinline__ bool stage_obs32_row(OP obs, int64_t i, int64_t B, co
 // the RCBF_WT_OUT study build.  GP: the buffers come as gptr (k_safe_steps), so every access is a global_*
 // instruction by type; k_safe_step passes its kernel arguments as they are.  OBS_SC1: the staged observation
 // chunks' store flavour (st_out4); OBS_PLAIN: plain stores instead (k_safe_steps_traj's study switch).
+// TERM (k_safe_steps_term): a step that resets its env also stores, at term_obs[i], the observation of the
+// post-step state BEFORE the reset -- the row this step would have stored with auto_reset = 0, bit for bit (the
+// same env_obs / uni_obs_cs arithmetic and fp64 -> fp32 conversion) -- as per-lane `nt` dword stores; a step
+// that does not reset writes nothing there.  Everything else a step computes and stores is as with TERM off,
+// and with TERM off every statement about it is discarded.
 template <int SOLVER, int MODE, int K, bool ST, bool WT, bool GP = false,
-          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, bool OBS_PLAIN = false, int CARRY = 0>
+          bool OBS_SC1 = WT || MODE == RCBF_MODE_SIMULATED_CARS, bool OBS_PLAIN = false, int CARRY = 0,
+          bool TERM = false>
 __device__ __forceinline__ void safe_step_body(
     const rcbf_params& prm, int64_t B, int64_t i, ptr_g<GP, double> __restrict__ x, ptr_g<GP, double> __restrict__ aux,
     ptr_g<GP, int32_t> __restrict__ step, ptr_g<GP, uint32_t> __restrict__ episode,
@@ -274,8 +280,11 @@ __device__ __forceinline__ void safe_step_body(
     uint64_t seed, int64_t off, double* xs, double& a, int& st, const float* us, const float* m, const float* s,
     bool ep_pre, uint32_t ep0, const Stamps<ST>& stamps, float* obs_stage, char* wt_lds, int lane,
     bool* did_reset = nullptr, float* obs_c = nullptr, float (*G_c)[Dims<MODE, K>::N] = nullptr,
-    float* h_c = nullptr, const float* u_nx = nullptr) {
+    float* h_c = nullptr, const float* u_nx = nullptr, ptr_g<GP, float> term_obs = nullptr) {
     using D = Dims<MODE, K>;
+    static_assert(!TERM || (GP && !ST && !WT && SOLVER == RCBF_SOLVER_ACTIVE_SET &&
+                            (MODE != RCBF_MODE_SIMULATED_CARS || RCBF_EARLY_STORE)),
+                  "the terminal observation: the fused loop only");
     static_assert(CARRY == 0 || (MODE == RCBF_MODE_SIMULATED_CARS && RCBF_EARLY_STORE && !ST && !WT && GP &&
                                  SOLVER == RCBF_SOLVER_ACTIVE_SET && RCBF_FUSED_RAW_ROWS != 0),
                   "the carried observation: the cars fused loop only");
@@ -329,6 +338,16 @@ __device__ __forceinline__ void safe_step_body(
         gm = false;
         const bool rs = auto_reset && dn;
         if (rs) {
+            if constexpr (TERM) {
+                // the terminal row but for car 3's velocity (component 7), which follows the solve
+                double ot[D::NO];
+                env_obs<MODE>(xs, ot);
+#pragma unroll
+                for (int k = 0; k < D::NO; ++k)
+                    if (k != 7) st_out(&term_obs[i * D::NO + k], (float)ot[k]);
+                oc[0] = xs[7];  // car 3's velocity before the reset, which the action below completes (oc is
+                                // otherwise the unicycle's: nothing else on this path reads it)
+            }
             const uint32_t ep = episode ? (ep_pre ? ep0 : episode[i]) + 1u : 0u;
             if (episode) {
                 if constexpr (WT)
@@ -360,13 +379,38 @@ __device__ __forceinline__ void safe_step_body(
         }
         status = L.qp.status;
         const double v3_reset = xs[7];
+        if constexpr (TERM) xs[7] = rs ? oc[0] : xs[7];  // a resetting lane finishes the velocity it had
         cars_env_post<float>(xs, acc3, uf[0], o);  // car 3's velocity and the reward
+        if constexpr (TERM) {
+            if (rs) st_out(&term_obs[i * D::NO + 7], (float)div_const(xs[7], 30.0, 1.0 / 30.0));  // cars_obs
+        }
         xs[7] = rs ? v3_reset : xs[7];
         rew = o.reward;
         st_any2d<WT>(&x[2 * (3 * B + i)], xs[6], xs[7]);
     } else {
-        safe_step_one<SOLVER, MODE, K, ST, WT>(prm, i, xs, a, st, episode, us, m, s, uf, rew, cst, dn, gm, status,
-                                               auto_reset, seed, off, stamps, oc, ep_pre, ep0);
+        if constexpr (TERM) {
+            static_assert(MODE == RCBF_MODE_UNICYCLE, "the cars loop takes the early-store path");
+            // the step without its reset (oc: cos, sin and goal distance of the post-step state) ...
+            safe_step_one<SOLVER, MODE, K, ST, WT>(prm, i, xs, a, st, episode, us, m, s, uf, rew, cst, dn, gm, status,
+                                                   0, seed, off, stamps, oc, ep_pre, ep0);
+            if (auto_reset && dn) {
+                // ... the row store_obs32 would store of it, then the reset, in safe_step_one's statements
+                double ot[D::NO];
+                uni_obs_cs(xs, oc[0], oc[1], oc[2], ot);
+#pragma unroll
+                for (int k = 0; k < D::NO; ++k) st_out(&term_obs[i * D::NO + k], (float)ot[k]);
+                const uint32_t ep = episode ? (ep_pre ? ep0 : episode[i]) + 1u : 0u;
+                if (episode) episode[i] = ep;
+                env_reset_one<MODE>(nullptr, i, seed, off, ep, xs, a, st);
+                oc[0] = 1.0;  // the reset state's obs inputs
+                oc[1] = 0.0;
+                oc[2] = a;
+                oc[3] = 1.0;
+            }
+        } else {
+            safe_step_one<SOLVER, MODE, K, ST, WT>(prm, i, xs, a, st, episode, us, m, s, uf, rew, cst, dn, gm, status,
+                                                   auto_reset, seed, off, stamps, oc, ep_pre, ep0);
+        }
         if constexpr (WT) {
 #pragma unroll
             for (int p = 0; p < D::NS / 2; ++p) st_wt2d(&x[2 * (p * B + i)], xs[2 * p], xs[2 * p + 1]);
@@ -688,6 +732,30 @@ __device__ __forceinline__ TrajTail* traj_stage_of(int wave) {
     return &stage[wave];
 }
 
+// The trajectory form that also keeps the terminal observation (rcbf_aql_safe_step_term_plan, traj_mask with
+// RCBF_TRAJ_TERM_OBS): k_safe_steps_traj with one more recorded pointer, term_obs, the base of a dense
+// (steps, P, n_o) fp32 array.  A step j that resets env i stores at [j][i] the observation of env i's post-step
+// state before the reset (safe_step_body, TERM); nothing else of the array is written.  The pointer is moved on
+// by one row per step like the other recorded pointers.  Its argument block is SafeStepsTrajArgs + term_obs:
+struct SafeStepsTermArgs {
+    SafeStepsTrajArgs t;
+    float* term_obs;
+};
+static_assert(offsetof(SafeStepsTermArgs, term_obs) == 424 && sizeof(SafeStepsTermArgs) == 432, "kernarg layout");
+
+// ... read from the argument segment like traj_mask and traj_pitch (the loop's source names no parameter that
+// only one of the three kernels has)
+__device__ __forceinline__ gptr<float> term_from_kernargs() {
+    uint64_t p = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const char __attribute__((address_space(4)))* cbytes_t;
+    const cbytes_t ka = (cbytes_t)__builtin_amdgcn_kernarg_segment_ptr();
+    p = *reinterpret_cast<const uint64_t __attribute__((address_space(4)))*>(
+        ka + offsetof(SafeStepsTermArgs, term_obs));
+#endif
+    return reinterpret_cast<gptr<float>>(p);
+}
+
 // The loop's source is one file, rcbf_safe_steps_loop.inc, included as the body of both kernels: with TRAJ =
 // false every `if constexpr (TRAJ)` in it is discarded and k_safe_steps is, statement for statement, the
 // kernel it was before the trajectory form existed (and compiles to the same machine code, which a common
@@ -705,7 +773,9 @@ __global__ void __launch_bounds__(BS) k_safe_steps(int64_t B, double* __restrict
                                                        int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
                                                        int prior_cols, int n_u, int steps, int ju0) {
     constexpr bool TRAJ = false;
+#define RCBF_LOOP_TERM 0
 #include "rcbf_safe_steps_loop.inc"
+#undef RCBF_LOOP_TERM
 }
 
 // The trajectory form (SafeStepsTrajArgs above).  traj_mask and traj_pitch are part of the argument block and
@@ -721,7 +791,27 @@ __global__ void __launch_bounds__(BS) k_safe_steps_traj(
     (void)traj_mask;
     (void)traj_pitch;
     constexpr bool TRAJ = true;
+#define RCBF_LOOP_TERM 0
 #include "rcbf_safe_steps_loop.inc"
+#undef RCBF_LOOP_TERM
+}
+
+// The trajectory form that also keeps the terminal observation (SafeStepsTermArgs above).
+template <int MODE, int K, int BS = kBlock>
+__global__ void __launch_bounds__(BS) k_safe_steps_term(
+    int64_t B, double* __restrict__ x, double* __restrict__ aux, int32_t* __restrict__ step,
+    const float* const* __restrict__ u_tab, uint32_t* __restrict__ episode, const float* __restrict__ mu,
+    const float* __restrict__ sigma, float* __restrict__ obs_out, float* __restrict__ u_out,
+    float* __restrict__ reward, float* __restrict__ cost, uint8_t* __restrict__ done, uint8_t* __restrict__ goal_met,
+    int32_t* __restrict__ status_out, int32_t* fail_flag, int auto_reset, uint64_t seed, int64_t off, rcbf_params prm,
+    int prior_cols, int n_u, int steps, int ju0, int32_t traj_mask, int64_t traj_pitch, float* __restrict__ term_obs) {
+    (void)traj_mask;
+    (void)traj_pitch;
+    (void)term_obs;
+    constexpr bool TRAJ = true;
+#define RCBF_LOOP_TERM 1
+#include "rcbf_safe_steps_loop.inc"
+#undef RCBF_LOOP_TERM
 }
 
 // Explicit instantiation of k_safe_steps for every mode / hazard count and
@@ -748,5 +838,18 @@ __global__ void __launch_bounds__(BS) k_safe_steps_traj(
     RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, 64);  \
     RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, 128); \
     RCBF_SAFE_STEPS_TRAJ_INSTANTIATE_BS(MODE_, K_, 256)
+
+// ... and of k_safe_steps_term (rcbf_steps_term.hip): the same 27
+#define RCBF_SAFE_STEPS_TERM_INSTANTIATE_BS(MODE_, K_, BS_)                                                         \
+    template __global__ void k_safe_steps_term<MODE_, K_, BS_>(                                                     \
+        int64_t, double* __restrict__, double* __restrict__, int32_t* __restrict__, const float* const* __restrict__, \
+        uint32_t* __restrict__, const float* __restrict__, const float* __restrict__, float* __restrict__,          \
+        float* __restrict__, float* __restrict__, float* __restrict__, uint8_t* __restrict__, uint8_t* __restrict__, \
+        int32_t* __restrict__, int32_t*, int, uint64_t, int64_t, rcbf_params, int, int, int, int, int32_t, int64_t, \
+        float* __restrict__)
+#define RCBF_SAFE_STEPS_TERM_INSTANTIATE(MODE_, K_)      \
+    RCBF_SAFE_STEPS_TERM_INSTANTIATE_BS(MODE_, K_, 64);  \
+    RCBF_SAFE_STEPS_TERM_INSTANTIATE_BS(MODE_, K_, 128); \
+    RCBF_SAFE_STEPS_TERM_INSTANTIATE_BS(MODE_, K_, 256)
 
 }  // namespace rcbf

@@ -1,7 +1,11 @@
-    // rcbf_safe_steps_loop.inc -- the body of rcbf::k_safe_steps and rcbf::k_safe_steps_traj (rcbf_safe_step.hpp,
-    // which includes this file once in each, after `constexpr bool TRAJ`): the prologue that loads env i's state,
-    // first actions and priors, and the loop that runs env i's steps.  Not a header: it names the kernels'
-    // parameters (B, x, ..., prm, prior_cols, n_u, steps, ju0) and template parameters (MODE, K, BS).
+    // rcbf_safe_steps_loop.inc -- the body of rcbf::k_safe_steps, rcbf::k_safe_steps_traj and
+    // rcbf::k_safe_steps_term (rcbf_safe_step.hpp, which includes this file once in each, after `constexpr bool
+    // TRAJ` and `#define RCBF_LOOP_TERM`, 1 in the last only): the prologue that loads env i's state, first
+    // actions and priors, and the loop that runs env i's steps.  Not a header: it names the kernels' parameters
+    // (B, x, ..., prm, prior_cols, n_u, steps, ju0) and template parameters (MODE, K, BS).
+    // RCBF_LOOP_TERM is a preprocessor switch, not a third `if constexpr`: with the terminal pointer merely
+    // declared in all three, the cars k_safe_steps_traj kernels came out with their prologue's register copies
+    // in another order; this way the other two kernels' token stream is the one they had.
     using D = Dims<MODE, K>;
     constexpr int SOLVER = RCBF_SOLVER_ACTIVE_SET;
     constexpr bool WT = false;
@@ -110,6 +114,12 @@
                      "+a"(unextv));                                                                              \
     }
     RCBF_OPAQUE_V();  // once: uniform values, kept in accumulation registers from here on
+#if RCBF_LOOP_TERM
+    // the terminal observations' pointer, one more recorded pointer in an accumulation register
+    static_assert(TRAJ && !PLAIN, "k_safe_steps_term: a trajectory kernel");
+    gptr<float> termv = term_from_kernargs();
+    asm volatile("" : "+a"(termv));
+#endif
     // Everything loaded so far has arrived before the loop is entered (vmcnt(0); expcnt and lgkmcnt left
     // alone).  A wait for one of these loads inside the loop would be passed again in every step, where all
     // it can wait for is the last step's stores.
@@ -136,6 +146,9 @@
 #pragma nounroll
     while (leftv > 0) {
         RCBF_OPAQUE_V();  // every step: nothing derived from them is loop-invariant to the compiler
+#if RCBF_LOOP_TERM
+        asm volatile("" : "+a"(termv));
+#endif
         // The plain cars loop has no scalar register to spare (with the rows carried too, RCBF_FUSED_CARRY == 2,
         // it spilled four): the two pointers that only a reset and a failed solve use, as per-lane values (no
         // instruction).  Their null tests and env i's addresses are then worked out where those rare paths
@@ -190,10 +203,17 @@
         }
         bool rs = false;
         constexpr bool OBS_PLAIN = TRAJ && RCBF_TRAJ_OBS_PLAIN != 0;  // study switch (rcbf_safe_step.hpp)
+#if RCBF_LOOP_TERM
+        safe_step_body<SOLVER, MODE, K, false, WT, true, OBS_SC1, OBS_PLAIN, CARRY, true>(
+            prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv, costv, donev, goalv, statv, failv, arv, seedv, offv, xs,
+            a, st, us, m, s, epv != nullptr, epr, stamps, obs_stage[widv], nullptr, lanev, &rs, CARRY ? obs_c : nullptr,
+            CARRY ? Gc : nullptr, CARRY ? hc : nullptr, CARRY ? un : nullptr, termv);
+#else
         safe_step_body<SOLVER, MODE, K, false, WT, true, OBS_SC1, OBS_PLAIN, CARRY>(
             prm_j, Bv, i, xv, auxv, stepv, epv, obsv, uv, rewv, costv, donev, goalv, statv, failv, arv, seedv, offv, xs,
             a, st, us, m, s, epv != nullptr, epr, stamps, obs_stage[widv], nullptr, lanev, &rs, CARRY ? obs_c : nullptr, CARRY ? Gc : nullptr, CARRY ? hc : nullptr,
             CARRY ? un : nullptr);
+#endif
         epr += rs ? 1u : 0u;  // a reset stored epr + 1
         // this step's chunk reads of obs_stage stay ahead of the next step's writes to it (one wave's LDS
         // operations execute in order; this keeps the compiler from reordering them)
@@ -224,6 +244,9 @@
             donev += (t.mask & RCBF_TRAJ_DONE) ? row : (int64_t)0;
             goalv += (t.mask & RCBF_TRAJ_GOAL_MET) ? row : (int64_t)0;
             statv += (t.mask & RCBF_TRAJ_STATUS) ? row : (int64_t)0;
+#if RCBF_LOOP_TERM
+            termv += (t.mask & RCBF_TRAJ_TERM_OBS) ? row * D::NO : (int64_t)0;
+#endif
         }
 #pragma unroll
         for (int c = 0; c < D::NU; ++c) us[c] = un[c];

@@ -126,6 +126,14 @@ SIGNATURES = {
     "rcbf_aql_safe_step_traj_plan": [_P, _PRM, _I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _I32, _U64, _I64, _P, _I32, _I32, _I64,
                                      ctypes.POINTER(ctypes.c_void_p)],
+    # ... + traj_mask, traj_pitch, term_obs (RCBF_TRAJ_TERM_OBS: the pre-reset observation of a resetting step)
+    "rcbf_aql_safe_step_term_plan": [_P, _PRM, _I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _I32, _U64, _I64, _P, _I32, _I32, _I64, _P,
+                                     ctypes.POINTER(ctypes.c_void_p)],
+    # a trajectory's K B transitions into the replay ring: ring, capacity, position, B, K, P, n_o, n_u, obs0,
+    # step0, obs, term_obs, u, reward, done, max_episode_steps, dt, auto_reset, stream
+    "rcbf_traj_pack_replay_f64": [_P, _I64, _I64, _I64, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32,
+                                  ctypes.c_double, _I32, _P],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],

@@ -23,6 +23,13 @@ of each recorded field's (K, B[, w]) array instead of overwriting the one
 rollouts need from steps whose actions are known beforehand.  It takes the
 same two forms (fused: the k_safe_steps_traj kernels).  `plan.trajectory` is
 the dict; after `run()` the env and the outputs dict are as after a plain plan.
+With a "term_obs" field (`env.make_trajectory(K, fields + ("term_obs",))`) the
+plan also keeps, at [j][i] of that array, the TERMINAL observation of an env
+that step j auto-resets (obs[j][i] is then the next episode's first row);
+every other element of the array is left as it was.  Such a plan is always
+fused (the k_safe_steps_term kernels, K = 1 included): where it would have to
+be per-step, safe_step_plan raises.  `ReplayMemory.push_trajectory` packs the
+result into replay records.
 
 The queue is not a HIP stream: `run()` first waits for all HIP work queued
 on the env's device unless `sync_hip=False` is
@@ -43,6 +50,9 @@ PER_STEP = 128  # RCBF_AQL_PER_STEP: K dispatches even where the fused form appl
 TRAJ_OBS, TRAJ_U, TRAJ_REWARD, TRAJ_COST, TRAJ_DONE, TRAJ_GOAL_MET, TRAJ_STATUS = 1, 2, 4, 8, 16, 32, 64
 TRAJ_BITS = {"obs": TRAJ_OBS, "u": TRAJ_U, "reward": TRAJ_REWARD, "cost": TRAJ_COST, "done": TRAJ_DONE,
              "goal_met": TRAJ_GOAL_MET, "status": TRAJ_STATUS}
+# RCBF_TRAJ_TERM_OBS: a side output, not one of the step's outputs (so not in TRAJ_BITS): the observation of the
+# post-step state of a step that auto-resets, before the reset (trajectory["term_obs"])
+TRAJ_TERM_OBS = 128
 
 
 def _bind():
@@ -98,7 +108,9 @@ class AqlQueue:
         views, K' >= K, of pitch-padded arrays as env.make_trajectory
         returns them, whose keys select the recorded fields: step j writes
         row j of each (on a step that resets, obs[j] is the next episode's
-        first observation).  Not with span."""
+        first observation, and term_obs[j], if that field is there, the
+        finished episode's last).  Not with span; with "term_obs" the plan
+        must be fused (module docstring)."""
         if env.device != self.device:
             raise ValueError(f"env on {env.device}, queue on {self.device}")
         o = outputs if outputs is not None else env.make_outputs()
@@ -134,6 +146,11 @@ class AqlQueue:
                 raise ValueError("a trajectory plan takes no span buffer")
             traj = env.make_trajectory(K) if trajectory is True else dict(trajectory)
             mask, pitch = _trajectory_args(env, traj, K)
+            term = traj.get("term_obs")
+            if term is not None:
+                why = _term_plan_refusal(env, layer, us, term, K, pitch, profile, fused, fence_flags)
+                if why:
+                    raise ValueError(f"a trajectory plan with term_obs is always fused, but {why}")
             # a[9:17]: obs, u, reward, cost, done, goal_met, status, fail_flag -- a recorded field's pointer is
             # its array's base; the cars goal_met is never recorded (env._step_args passes none either)
             outs = list(a[9:17])
@@ -141,8 +158,14 @@ class AqlQueue:
                 if mask & TRAJ_BITS[f]:
                     outs[j] = traj[f].data_ptr()
             with torch.cuda.device(self.device):
-                _check(_lib.load().rcbf_aql_safe_step_traj_plan(*head, *[v or None for v in outs], *tail, mask, pitch,
-                                                                ctypes.byref(h)), "rcbf_aql_safe_step_traj_plan")
+                if term is not None:
+                    _check(_lib.load().rcbf_aql_safe_step_term_plan(
+                        *head, *[v or None for v in outs], *tail, mask | TRAJ_TERM_OBS, pitch, term.data_ptr(),
+                        ctypes.byref(h)), "rcbf_aql_safe_step_term_plan")
+                else:
+                    _check(_lib.load().rcbf_aql_safe_step_traj_plan(
+                        *head, *[v or None for v in outs], *tail, mask, pitch, ctypes.byref(h)),
+                        "rcbf_aql_safe_step_traj_plan")
         else:
             with torch.cuda.device(self.device):
                 _check(_lib.load().rcbf_aql_safe_step_plan(*head, *[v or None for v in a[9:17]], *tail,
@@ -184,8 +207,28 @@ def _trajectory_args(env, traj, K):
         pitch = p
         if f == "goal_met" and cars:
             continue  # never met: stays as make_trajectory zero-filled it
+        if f == "term_obs":
+            continue  # RCBF_TRAJ_TERM_OBS: set by the caller, which passes the pointer as well
         mask |= TRAJ_BITS[f]
     return mask, (pitch or 0)
+
+
+def _term_plan_refusal(env, layer, us, term, K, pitch, profile, fused, fence_flags):
+    """Why a plan that records term_obs could not take the fused form (the
+    library would answer RCBF_E_BAD_MODE), or None."""
+    if layer._prm.solver != _lib.SOLVER_ACTIVE_SET:
+        return "the layer's solver is not the exact active set"
+    if profile:
+        return "profile=True asks for per-dispatch timestamps"
+    if fused is False:
+        return "fused=False asks for the per-step form"
+    if int(fence_flags) & (8 | 16 | 32 | PER_STEP | PROFILE):
+        return "fence_flags asks for the per-step form"
+    lo, n = term.data_ptr(), K * pitch * env.n_o * 4
+    for u in us:
+        if u.data_ptr() < lo + n and lo < u.data_ptr() + u.numel() * 4:
+            return "an action buffer lies inside term_obs's extent"
+    return None
 
 
 class AqlPlan:
@@ -211,6 +254,8 @@ class AqlPlan:
         if self.trajectory is not None and copy_back:
             o = self._keep[2]
             for f, t in self.trajectory.items():
+                if f == "term_obs":
+                    continue  # a side output: no buffer of the env or the outputs dict corresponds to it
                 dst = self._env.obs if f == "obs" else o.get(f)
                 if dst is not None and not (f == "goal_met" and self._env.dynamics_mode == "SimulatedCars"):
                     dst.copy_(t[self.K - 1])

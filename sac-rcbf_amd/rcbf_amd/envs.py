@@ -434,12 +434,13 @@ class BatchedEnv:
         plan's recordable outputs (AqlQueue.safe_step_plan(trajectory=...))."""
         return {"obs": (self.n_o, torch.float32), "u": (self.n_u, torch.float32), "reward": (0, torch.float32),
                 "cost": (0, torch.float32), "done": (0, torch.uint8), "goal_met": (0, torch.uint8),
-                "status": (0, torch.int32)}
+                "status": (0, torch.int32), "term_obs": (self.n_o, torch.float32)}
 
     def make_trajectory(self, K, fields=TRAJECTORY_FIELDS):
         """Per-step output arrays for a K-step trajectory plan
         (AqlQueue.safe_step_plan(..., trajectory=...)): each field of `fields`
-        (TRAJECTORY_FIELDS, or "status": the QP status, int32) as a (K, B[, w])
+        (TRAJECTORY_FIELDS, "status": the QP status, int32, or "term_obs": the
+        pre-reset observation of a step that auto-resets, see rcbf_amd.aql) as a (K, B[, w])
         view of a dense (K, P[, w]) array, P = B rounded up to a multiple of 64
         (every row of every field starts on a 16-byte boundary, which the
         kernel's observation stores need); the pitch is stride(0) / w.  Step j

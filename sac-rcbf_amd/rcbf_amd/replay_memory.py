@@ -13,8 +13,14 @@ so the sampled indices differ from the reference's stream).
 sample() returns numpy arrays like the reference (mask as float64, t/next_t
 NaN when they were pushed as None); sample_tensors() keeps them on the device
 for the SAC update.
+
+push_trajectory() takes the arrays of a K-step trajectory plan (rcbf_amd.aql)
+and writes their K x B transitions into the ring in one launch
+(rcbf_traj_pack_replay_f64): what the warm-up loop's memory.push per step
+(main.py:100-107) leaves, terminal observations included.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -79,6 +85,71 @@ class ReplayMemory:
         rc = _lib.load().rcbf_ring_scatter_f64(_lib.ptr(self._ring), self.capacity, rec.shape[1], self.position,
                                                _lib.ptr(rec), n, _lib.stream_of(self.device))
         _lib.check(rc, "rcbf_ring_scatter_f64")
+        self.position = (self.position + n) % self.capacity
+        self._size = min(self._size + n, self.capacity)
+
+    def push_trajectory(self, env, traj, obs0, step0, rows=None, auto_reset=True):
+        """The `rows` (default: all) steps of a trajectory plan of `env`
+        (AqlQueue.safe_step_plan(trajectory=traj)) as rows x B transitions, in
+        the order B envs stepped in lock-step would push them (step-major):
+        one rcbf_traj_pack_replay_f64 launch, no intermediate tensor.
+        obs0 (B, n_o) f32: the observation step 0 acted on (env.obs before the
+        run, cloned); step0 (B,) i32: env.step_count before the run, cloned.
+        traj needs "obs", "u", "reward", "done"; with "term_obs" (and
+        auto_reset, as the plan ran) the next_obs of a transition that ended
+        an episode is the terminal observation, without it the next episode's
+        first (warned about once).  mask, t and next_t follow main.py:100-107:
+        mask 1 at the time limit, else 1 - done; t the episode step x dt."""
+        B, n_o, n_u = env.num_envs, env.n_o, env.n_u
+        for f in ("obs", "u", "reward", "done"):
+            if f not in traj:
+                raise ValueError(f"push_trajectory needs trajectory[{f!r}]")
+        spec = env._trajectory_spec()
+        fields = {f: traj[f] for f in ("obs", "u", "reward", "done", "term_obs") if traj.get(f) is not None}
+        K = min(int(t.shape[0]) for t in fields.values()) if rows is None else int(rows)
+        pitch = None
+        for f, t in fields.items():
+            w, dt = spec[f]
+            want = (B, w) if w else (B,)
+            if not (torch.is_tensor(t) and t.dtype == dt and t.device == self.device and t.dim() == len(want) + 1
+                    and tuple(t.shape[1:]) == want):
+                raise ValueError(f"trajectory[{f!r}] must be a {dt} tensor of shape (K, {', '.join(map(str, want))}) "
+                                 f"on {self.device}")
+            ww = w or 1
+            st = t.stride()
+            if st[1:] != ((w, 1) if w else (1,)) or st[0] % ww or st[0] // ww < B:
+                raise ValueError(f"trajectory[{f!r}] must be a [:, :B] view of a dense (K, P{', w' if w else ''}) "
+                                 f"array (use env.make_trajectory), got strides {st}")
+            if pitch is not None and st[0] // ww != pitch:
+                raise ValueError(f"trajectory[{f!r}] has row pitch {st[0] // ww}, the other fields {pitch}")
+            pitch = st[0] // ww
+            if t.shape[0] < K:
+                raise ValueError(f"trajectory[{f!r}] has {t.shape[0]} rows, rows = {K}")
+        if K <= 0:
+            raise ValueError(f"rows must be positive, got {K}")
+        if not (torch.is_tensor(obs0) and obs0.dtype == torch.float32 and obs0.device == self.device
+                and tuple(obs0.shape) == (B, n_o) and obs0.is_contiguous()):
+            raise ValueError(f"obs0 must be a contiguous float32 tensor of shape ({B}, {n_o}) on {self.device}")
+        if not (torch.is_tensor(step0) and step0.dtype == torch.int32 and step0.device == self.device
+                and tuple(step0.shape) == (B,) and step0.is_contiguous()):
+            raise ValueError(f"step0 must be a contiguous int32 tensor of shape ({B},) on {self.device}")
+        term = fields.get("term_obs")
+        if term is None and auto_reset and not getattr(self, "_warned_no_term_obs", False):
+            self._warned_no_term_obs = True
+            warnings.warn("push_trajectory without trajectory['term_obs']: the next_obs of a transition that ends an "
+                          "episode is the next episode's first observation (record term_obs with the plan)")
+        if self._dims is None:
+            self._dims = (n_o, n_u)
+            self._ring = torch.empty(self.capacity, self._width(), dtype=torch.float64, device=self.device)
+        if (n_o, n_u) != self._dims:
+            raise ValueError(f"transition shapes {(n_o, n_u)} != {self._dims}")
+        rc = _lib.load().rcbf_traj_pack_replay_f64(
+            _lib.ptr(self._ring), self.capacity, self.position, B, K, pitch, n_o, n_u, _lib.ptr(obs0),
+            _lib.ptr(step0), _lib.ptr(fields["obs"]), _lib.ptr(term), _lib.ptr(fields["u"]),
+            _lib.ptr(fields["reward"]), _lib.ptr(fields["done"]), int(env.max_episode_steps), float(env.dt),
+            int(bool(auto_reset)), _lib.stream_of(self.device))
+        _lib.check(rc, "rcbf_traj_pack_replay_f64")
+        n = K * B
         self.position = (self.position + n) % self.capacity
         self._size = min(self._size + n, self.capacity)
 
