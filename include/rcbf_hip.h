@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RCBF_ABI_VERSION 12
+#define RCBF_ABI_VERSION 13
 
 /* dynamics modes: rcbf_sac/dynamics.py:22-23 DYNAMICS_MODE */
 #define RCBF_MODE_SIMULATED_CARS 0
@@ -394,6 +394,48 @@ int rcbf_traj_pack_replay_f64(double* ring, int64_t capacity, int64_t position, 
                               int32_t n_o, int32_t n_u, const float* obs0, const int32_t* step0, const float* obs,
                               const float* term_obs, const float* u, const float* reward, const uint8_t* done,
                               int32_t max_episode_steps, double dt, int32_t auto_reset, hipStream_t stream);
+
+/* The transitions of a trajectory plan (rcbf_aql_safe_step_term_plan) that
+ * the reference's loop hands to DynamicsModel.append_transition
+ * (main.py:110-113: state = get_state(obs), next_state = get_state(next_obs),
+ * on every second episode step append_transition(state, action, next_state,
+ * t_batch=[episode_steps * dt])), as the rows (x, d) append_transition stores
+ * (rcbf_sac/dynamics.py:263-303), compacted into two dense fp64 arrays.  The
+ * arithmetic is on the device; three launches on `stream` (count, scan, pack),
+ * no host synchronisation, no atomics: the result is the same in every run.
+ * Inputs as rcbf_traj_pack_replay_f64 (no reward).  For transition (j, i), with
+ * c = step0[i] before step 0:
+ *   e = c + 1; then c = (done and auto_reset) ? 0 : e
+ *   selected iff e % every == 0 (the reference: every = 2)
+ *   obs_prev = obs0[i] for j = 0, else obs[j-1][i]
+ *   next_obs = term_obs[j][i] if done[j][i] and auto_reset, else obs[j][i]
+ *   x = get_state(obs_prev), x' = get_state(next_obs): fp32 widened exactly,
+ *     cars x100 / x30, unicycle atan2(o[3], o[2]) (dynamics.py:190-232, numpy)
+ *   t = (double)e * dt; F = f(x, t) + g(x) u, u widened from fp32
+ *     (dynamics.py:125-188, in DynamicsModel._f_plus_gu's operation order)
+ *   d = ((x' - x) - dt F) / dt
+ * all fp64 without contraction: every column is bit-reproducible from the
+ * inputs but those a transcendental reaches (cars d[1]: sin; unicycle x[2],
+ * d[0..2]: atan2, cos, sin; ocml).
+ * term_obs may be null only when auto_reset == 0 (RCBF_E_NULL): a reset row as
+ * x' would be a garbage disturbance.
+ * The n_sel selected transitions are numbered step-major, env-minor (the
+ * order in which B envs stepped in lock-step make the reference's calls).
+ * rows = min(n_sel, keep_last) rows are written: row r of state_out and of
+ * dist_out, each (rows, n_s) f64 dense, is selected transition
+ * n_sel - rows + r -- what sequential appends leave in a ring of keep_last
+ * rows.  Nothing outside [0, rows) is written.  The caller's arrays hold
+ * min(B * ceil(K / every), keep_last) rows (no env selects more than
+ * ceil(K / every) steps: a reset only delays its next selection).
+ * count_out: int64[2] on the device = {n_sel, rows}.  scratch: caller-owned,
+ * rcbf_traj_pack_gp_scratch_bytes(B, K) bytes, 8-byte aligned, contents
+ * undefined before and after.  every >= 1, keep_last >= 1; (n_o, n_u) = (10, 1)
+ * or (7, 2); cars rows 8-byte aligned as in rcbf_traj_pack_replay_f64. */
+int64_t rcbf_traj_pack_gp_scratch_bytes(int64_t B, int32_t K);
+int rcbf_traj_pack_gp_f64(double* state_out, double* dist_out, int64_t* count_out, void* scratch, int64_t B,
+                          int32_t K, int64_t P, int32_t n_o, int32_t n_u, const float* obs0, const int32_t* step0,
+                          const float* obs, const float* term_obs, const float* u, const uint8_t* done, double dt,
+                          int32_t auto_reset, int32_t every, int64_t keep_last, hipStream_t stream);
 
 /* ReplayMemory.sample (replay_memory.py:31-35) gather: dst[r] = ring[idx[r]]. */
 int rcbf_gather_rows_f64(double* dst, const double* ring, int64_t W, const int64_t* idx,

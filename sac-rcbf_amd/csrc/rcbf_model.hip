@@ -94,11 +94,11 @@ __device__ __forceinline__ void model_state_from_obs(const double* o, double* xs
     }
 }
 
-// x + dt (f(x) + g(x) u) of the model prior (dynamics.py:60-105, 125-188)
+// f(x, t) + g(x) u of the model prior (dynamics.py:125-188), the rate itself: DynamicsModel._f_plus_gu
+// operation for operation, the `+ 0.0` of the zero f / gu entries included
 template <int MODE>
-__device__ __forceinline__ void model_prior_next(const double* xs, const double* u, double t, double* nx) {
+__device__ __forceinline__ void model_prior_rate(const double* xs, const double* u, double t, double* F) {
 #pragma clang fp contract(off)
-    const double dt = 0.02;
     if constexpr (MODE == RCBF_MODE_SIMULATED_CARS) {
         double pos[5], vel[5], acc[5];
 #pragma unroll
@@ -119,16 +119,28 @@ __device__ __forceinline__ void model_prior_next(const double* xs, const double*
         acc[4] -= 20.0 * d24 * (d24 < 13.0 ? 1.0 : 0.0);
 #pragma unroll
         for (int c = 0; c < 5; ++c) {
-            nx[2 * c] = xs[2 * c] + dt * (vel[c] + 0.0);
-            nx[2 * c + 1] = xs[2 * c + 1] + dt * (acc[c] + (c == 3 ? 50.0 * u[0] : 0.0));
+            F[2 * c] = vel[c] + 0.0;
+            F[2 * c + 1] = acc[c] + (c == 3 ? 50.0 * u[0] : 0.0);
         }
     } else {
         double s, c;
         sincos(xs[2], &s, &c);
-        nx[0] = xs[0] + dt * (0.0 + c * u[0]);
-        nx[1] = xs[1] + dt * (0.0 + s * u[0]);
-        nx[2] = xs[2] + dt * (0.0 + u[1]);
+        F[0] = 0.0 + c * u[0];
+        F[1] = 0.0 + s * u[0];
+        F[2] = 0.0 + u[1];
     }
+}
+
+// x + dt (f(x) + g(x) u) of the model prior (dynamics.py:60-105)
+template <int MODE>
+__device__ __forceinline__ void model_prior_next(const double* xs, const double* u, double t, double* nx) {
+#pragma clang fp contract(off)
+    constexpr int NS = Dims<MODE, 1>::NS;
+    const double dt = 0.02;
+    double F[NS];
+    model_prior_rate<MODE>(xs, u, t, F);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) nx[k] = xs[k] + dt * F[k];
 }
 
 template <int MODE>
@@ -332,6 +344,24 @@ __device__ __forceinline__ void run_out(double* __restrict__ ring, int64_t dst0,
     if (lane == 1 && ((n - head) & 1)) __builtin_nontemporal_store(s[n - 1], p + n - 1);
 }
 
+// a trajectory's observation row of NO floats (`nt`, read once): 8-byte pairs where rows are 8-byte aligned
+// (cars, 40 B), dwords otherwise (28 B)
+template <int NO>
+__device__ __forceinline__ void load_obs_row(const float* __restrict__ row, float* o) {
+    if constexpr (NO % 2 == 0) {
+        typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int k = 0; k < NO / 2; ++k) {
+            const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(row) + k);
+            o[2 * k] = v.x;
+            o[2 * k + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NO; ++k) o[k] = ld_in(&row[k]);
+    }
+}
+
 // rcbf_traj_pack_replay_f64: the K x B transitions of a trajectory plan as packed replay records, written
 // straight into the ring.  One env per lane, a wave per workgroup; the lane that owns env i walks steps
 // [j0, j1) = blockIdx.y's chunk of `chunk` steps, carrying env i's episode-step count (recomputed from
@@ -364,21 +394,6 @@ __global__ void __launch_bounds__(64) k_traj_pack_replay(double* __restrict__ ri
     const int nl = (int)(B - wbase < 64 ? B - wbase : 64);  // this wave's envs
     const int j0 = (int)blockIdx.y * chunk;
     const int j1 = j0 + chunk < K ? j0 + chunk : K;
-    // a row of NO floats: 8-byte pairs where rows are 8-byte aligned (cars, 40 B), dwords otherwise (28 B)
-    auto load_row = [](const float* __restrict__ row, float* o) {
-        if constexpr (NO % 2 == 0) {
-            typedef float f2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int k = 0; k < NO / 2; ++k) {
-                const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(row) + k);
-                o[2 * k] = v.x;
-                o[2 * k + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NO; ++k) o[k] = ld_in(&row[k]);
-        }
-    };
     int c = 0;
     float prev[NO];
 #pragma unroll
@@ -389,20 +404,20 @@ __global__ void __launch_bounds__(64) k_traj_pack_replay(double* __restrict__ ri
             const bool dn = ld_in(&done[(int64_t)j * P + i]) != 0;
             c = (dn && auto_reset) ? 0 : c + 1;
         }
-        load_row(j0 == 0 ? obs0 + i * NO : obs + ((int64_t)(j0 - 1) * P + i) * NO, prev);
+        load_obs_row<NO>(j0 == 0 ? obs0 + i * NO : obs + ((int64_t)(j0 - 1) * P + i) * NO, prev);
     }
     for (int j = j0; j < j1; ++j) {
         if (live) {
             const int64_t e = (int64_t)j * P + i;
             float cur[NO], nx[NO], uj[NU];
-            load_row(obs + e * NO, cur);
+            load_obs_row<NO>(obs + e * NO, cur);
 #pragma unroll
             for (int k = 0; k < NU; ++k) uj[k] = ld_in(&u[e * NU + k]);
             const float rw = ld_in(&reward[e]);
             const bool dn = ld_in(&done[e]) != 0;
 #pragma unroll
             for (int k = 0; k < NO; ++k) nx[k] = cur[k];
-            if (dn && auto_reset && term) load_row(term + e * NO, nx);  // rare: the episode's last observation
+            if (dn && auto_reset && term) load_obs_row<NO>(term + e * NO, nx);  // rare: the episode's last observation
             const int ep = c + 1;
             double* const rec = stage + lane * W;
 #pragma unroll
@@ -432,6 +447,250 @@ __global__ void __launch_bounds__(64) k_traj_pack_replay(double* __restrict__ ri
         }
         __syncthreads();  // ... and read, before the next step's records overwrite them
     }
+}
+
+// rcbf_traj_pack_gp_f64: the transitions of a trajectory plan that the reference's loop hands to
+// DynamicsModel.append_transition (main.py:110-113: every `every`-th episode step), as rows (x, d) of the GP's
+// disturbance dataset, compacted.  Which transitions are selected depends on the done bytes, so the work is
+// three launches on one stream: k_traj_gp_count (the selected lanes of each (step, wave), from a ballot),
+// k_traj_gp_scan (their exclusive prefix sum in step-major, wave-minor order: the slot of every wave's first
+// selected row of every step; one workgroup, fixed order, no atomics) and k_traj_pack_gp (the rows).
+
+// An env's episode-step count along the plan: c before a step, and r = c mod `every` carried beside it so that
+// "e = c + 1 is a multiple of `every`" costs no division per step.  The recurrence of k_traj_pack_replay.
+struct EpisodeStep {
+    int c, r;
+    __device__ __forceinline__ void start(int c0, int every) {
+        c = c0;
+        r = c0 % every;
+    }
+    // one step; returns e, and in `sel` whether the reference appends this transition
+    __device__ __forceinline__ int step(bool reset, int every, bool& sel) {
+        const int e = c + 1;
+        r = r + 1 == every ? 0 : r + 1;
+        sel = r == 0;
+        c = reset ? 0 : e;
+        if (reset) r = 0;
+        return e;
+    }
+    // the steps [0, j_end) of env i, from the done bytes alone: only the last reset before j_end matters (the
+    // count is the steps since it, or c0 + j_end without one), so the bytes are loaded 16 at a time, all 16 in
+    // flight together, and compared -- a load's latency per 16 steps instead of per step
+    __device__ __forceinline__ void walk(const uint8_t* __restrict__ done, int64_t P, int64_t i, int j_end,
+                                         int auto_reset, int every) {
+        if (j_end <= 0) return;
+        int last = -1;
+        if (auto_reset) {
+            int j = 0;
+            for (; j + 16 <= j_end; j += 16) {
+                uint8_t b[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) b[k] = ld_in(&done[(int64_t)(j + k) * P + i]);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) last = b[k] ? j + k : last;
+            }
+            for (; j < j_end; ++j) last = ld_in(&done[(int64_t)j * P + i]) ? j : last;
+        }
+        start(last >= 0 ? j_end - 1 - last : c + j_end, every);
+    }
+};
+
+// counts[j waves + w] = selected transitions among wave w's envs at step j.  Grid and chunks as k_traj_pack_gp.
+__global__ void __launch_bounds__(64) k_traj_gp_count(int64_t* __restrict__ counts, int64_t B, int K, int64_t P,
+                                                      const int32_t* __restrict__ step0,
+                                                      const uint8_t* __restrict__ done, int auto_reset, int every,
+                                                      int chunk) {
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = i < B;
+    const int j0 = (int)blockIdx.y * chunk;
+    const int j1 = j0 + chunk < K ? j0 + chunk : K;
+    EpisodeStep ep;
+    ep.start(live ? ld_in(&step0[i]) : 0, every);
+    if (live) ep.walk(done, P, i, j0, auto_reset, every);
+    for (int j = j0; j < j1; j += 8) {  // 8 steps' bytes in flight together
+        uint8_t b[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = (live && j + k < j1) ? ld_in(&done[(int64_t)(j + k) * P + i]) : 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (j + k < j1) {  // (wave-uniform)
+                bool sel = false;
+                if (live) ep.step(b[k] != 0 && auto_reset, every, sel);
+                const unsigned long long m = __ballot(sel);
+                if (lane == 0) counts[(int64_t)(j + k) * gridDim.x + blockIdx.x] = (int64_t)__popcll(m);
+            }
+        }
+    }
+}
+
+// v[0 .. n) (counts) -> their exclusive prefix sums, in place, and v[n] = the total; count_out = {total,
+// min(total, keep_last)}.  ONE workgroup: tiles of 1024 x 16 consecutive elements (a thread's 16 are contiguous,
+// all loaded before any is used), a wave scan of the thread sums, the 16 wave sums through LDS, the tiles'
+// total carried.  Same order of additions in every run; n is K x waves, 20 480 at B = 65 536, K = 20.
+__global__ void __launch_bounds__(1024) k_traj_gp_scan(int64_t* __restrict__ v, int64_t n, int64_t keep_last,
+                                                       int64_t* __restrict__ count_out) {
+    constexpr int kIt = 16;
+    __shared__ long long wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long carry = 0;
+    for (int64_t base = 0; base < n; base += 1024 * kIt) {
+        const int64_t e0 = base + (int64_t)threadIdx.x * kIt;
+        long long a[kIt];
+#pragma unroll
+        for (int k = 0; k < kIt; ++k) a[k] = e0 + k < n ? (long long)v[e0 + k] : 0;
+        long long tsum = 0;
+#pragma unroll
+        for (int k = 0; k < kIt; ++k) {
+            const long long t = a[k];
+            a[k] = tsum;
+            tsum += t;
+        }
+        long long inc = tsum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        long long before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const long long s = wsum[w];
+            if (w < wave) before += s;
+            total += s;
+        }
+        const long long ex = carry + before + (inc - tsum);
+#pragma unroll
+        for (int k = 0; k < kIt; ++k)
+            if (e0 + k < n) v[e0 + k] = (int64_t)(ex + a[k]);
+        carry += total;
+        __syncthreads();  // the wave sums are read before the next tile's replace them
+    }
+    if (threadIdx.x == 0) {
+        v[n] = (int64_t)carry;
+        count_out[0] = (int64_t)carry;
+        count_out[1] = (int64_t)(carry < keep_last ? carry : keep_last);
+    }
+}
+
+// The pack pass.  One env per lane, a wave per workgroup, steps [j0, j1) = blockIdx.y's chunk, the lane carrying
+// its env's step count and the row obs[j - 1][i] (x' of one transition, x of the next: loaded once), as
+// k_traj_pack_replay.  At step j the wave's selected lanes are ranked by a ballot; lane of rank q forms
+//   x = get_state(obs_prev), x' = get_state(next_obs), F = f(x, e dt) + g(x) u, d = ((x' - x) - dt F) / dt
+// (fp64, the numpy path's order: dynamics.py:190-232, :263-303) and writes both rows at row q of the wave's LDS
+// block.  The wave's rows of a step are rows offs[j waves + w] ... of the compacted result, ONE contiguous run
+// of each output, stored as 16-B lane vectors (run_out).  Only the last keep_last selected rows are kept: rows
+// before skip = n_sel - keep_last are not written, a workgroup whose chunk lies wholly before it ends at once,
+// and one that straddles it starts at the first step that has a kept row.
+template <int MODE>
+__global__ void __launch_bounds__(64) k_traj_pack_gp(double* __restrict__ state_out, double* __restrict__ dist_out,
+                                                     const int64_t* __restrict__ offs, int64_t keep_last, int64_t B,
+                                                     int K, int64_t P, const float* __restrict__ obs0,
+                                                     const int32_t* __restrict__ step0,
+                                                     const float* __restrict__ obs, const float* __restrict__ term,
+                                                     const float* __restrict__ u, const uint8_t* __restrict__ done,
+                                                     double dt, int auto_reset, int every, int chunk) {
+#pragma clang fp contract(off)
+    using D = Dims<MODE, 1>;
+    constexpr int NO = D::NO, NU = D::NU, NS = D::NS;
+    __shared__ __attribute__((aligned(16))) double stage_x[64 * NS];
+    __shared__ __attribute__((aligned(16))) double stage_d[64 * NS];
+    const int lane = threadIdx.x;
+    const int64_t w = blockIdx.x, waves = gridDim.x;
+    const int64_t i = w * 64 + lane;
+    const bool live = i < B;
+    const int j0 = (int)blockIdx.y * chunk;
+    const int j1 = j0 + chunk < K ? j0 + chunk : K;
+    const int64_t n_sel = offs[(int64_t)K * waves];
+    const int64_t skip = n_sel > keep_last ? n_sel - keep_last : 0;
+    // rows selected up to and including this wave's of step j
+    auto end_of = [&](int j) { return offs[(int64_t)j * waves + w + 1]; };
+    if (end_of(j1 - 1) <= skip) return;  // (wave-uniform) nothing of this chunk is kept, or nothing is selected
+    int ja = j0;
+    if (skip > 0) {  // the first step of the chunk with a kept row: the offsets are monotone
+        int hi = j1 - 1;
+        while (ja < hi) {
+            const int mid = (ja + hi) >> 1;
+            if (end_of(mid) > skip)
+                hi = mid;
+            else
+                ja = mid + 1;
+        }
+    }
+    EpisodeStep ep;
+    ep.start(live ? ld_in(&step0[i]) : 0, every);
+    float prev[NO];
+#pragma unroll
+    for (int k = 0; k < NO; ++k) prev[k] = 0.0f;
+    if (live) {
+        ep.walk(done, P, i, ja, auto_reset, every);
+        load_obs_row<NO>(ja == 0 ? obs0 + i * NO : obs + ((int64_t)(ja - 1) * P + i) * NO, prev);
+    }
+    for (int j = ja; j < j1; ++j) {
+        const int64_t e = (int64_t)j * P + i;
+        float cur[NO], uj[NU];
+        bool sel = false, reset = false;
+        int es = 0;
+        if (live) {
+            load_obs_row<NO>(obs + e * NO, cur);
+#pragma unroll
+            for (int k = 0; k < NU; ++k) uj[k] = ld_in(&u[e * NU + k]);
+            reset = ld_in(&done[e]) != 0 && auto_reset;
+            es = ep.step(reset, every, sel);
+        }
+        const unsigned long long m = __ballot(sel);
+        const int n_w = __popcll(m);
+        if (sel) {
+            const int q = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            float nx[NO];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) nx[k] = cur[k];
+            if (reset) load_obs_row<NO>(term + e * NO, nx);  // rare: the episode's last observation
+            double o[NO], x[NS], xn[NS], ud[NU], F[NS];
+#pragma unroll
+            for (int k = 0; k < NO; ++k) o[k] = (double)prev[k];
+            model_state_from_obs<MODE>(o, x);
+#pragma unroll
+            for (int k = 0; k < NO; ++k) o[k] = (double)nx[k];
+            model_state_from_obs<MODE>(o, xn);
+#pragma unroll
+            for (int k = 0; k < NU; ++k) ud[k] = (double)uj[k];
+            model_prior_rate<MODE>(x, ud, (double)es * dt, F);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                stage_x[q * NS + k] = x[k];
+                stage_d[q * NS + k] = ((xn[k] - x[k]) - dt * F[k]) / dt;
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < NO; ++k) prev[k] = cur[k];
+        }
+        __syncthreads();  // one wave: the rows are in LDS
+        // the wave's n_w rows of this step are rows g0, g0 + 1, ... of the selection; kept from row `skip` on
+        const int64_t g0 = offs[(int64_t)j * waves + w];
+        const int qa = skip > g0 ? (skip - g0 < n_w ? (int)(skip - g0) : n_w) : 0;
+        const int kept = n_w - qa;
+        if (kept > 0) {
+            const int64_t dst = (g0 + qa - skip) * NS;
+            run_out(state_out, dst, stage_x + qa * NS, kept * NS, lane);
+            run_out(dist_out, dst, stage_d + qa * NS, kept * NS, lane);
+        }
+        __syncthreads();  // ... and read, before the next step's rows overwrite them
+    }
+}
+
+// Steps per workgroup of the trajectory packers (one wave of envs per workgroup, K steps): the whole plan where
+// the batch alone fills the chip (8 waves a CU), shorter chunks (each lane then first re-derives its step count
+// from the done bytes before its chunk) where it does not.
+inline int traj_steps_per_workgroup(int64_t waves, int K) {
+    const int64_t want = (int64_t)num_cus() * 8;
+    int64_t parts = waves >= want ? 1 : (want + waves - 1) / waves;
+    if (parts > K) parts = K;
+    if (parts > 65535) parts = 65535;
+    return (int)((K + parts - 1) / parts);
 }
 
 }  // namespace
@@ -531,13 +790,8 @@ int rcbf_traj_pack_replay_f64(double* ring, int64_t capacity, int64_t position, 
     if ((((uintptr_t)ring) & 7) || B > INT32_MAX) return RCBF_E_BAD_SHAPE;
     const int64_t n = (int64_t)K * B;
     const int64_t skip = n > capacity ? n - capacity : 0;
-    // steps per workgroup: the whole plan where the batch alone fills the chip (8 waves a CU), shorter chunks
-    // (each lane then first re-derives its step count from the done bytes before its chunk) where it does not
-    const int64_t waves = (B + 63) / 64, want = (int64_t)num_cus() * 8;
-    int64_t parts = waves >= want ? 1 : (want + waves - 1) / waves;
-    if (parts > K) parts = K;
-    if (parts > 65535) parts = 65535;
-    const int chunk = (int)((K + parts - 1) / parts);
+    const int64_t waves = (B + 63) / 64;
+    const int chunk = traj_steps_per_workgroup(waves, K);
     const dim3 g((unsigned)waves, (unsigned)((K + chunk - 1) / chunk)), b(64);
     if (cars)
         hipLaunchKernelGGL((k_traj_pack_replay<DC::NO, DC::NU>), g, b, 0, stream, ring, capacity, position, skip, B,
@@ -547,6 +801,50 @@ int rcbf_traj_pack_replay_f64(double* ring, int64_t capacity, int64_t position, 
         hipLaunchKernelGGL((k_traj_pack_replay<DU::NO, DU::NU>), g, b, 0, stream, ring, capacity, position, skip, B,
                            (int)K, P, obs0, step0, obs, term_obs, u, reward, done, (int)max_episode_steps, dt,
                            (int)auto_reset, chunk);
+    return launch_status();
+}
+
+int64_t rcbf_traj_pack_gp_scratch_bytes(int64_t B, int32_t K) {
+    if (B < 0 || K <= 0) return 0;
+    return 8 * (((B + 63) / 64) * (int64_t)K + 1);  // a count per (step, wave), and the total
+}
+
+int rcbf_traj_pack_gp_f64(double* state_out, double* dist_out, int64_t* count_out, void* scratch, int64_t B,
+                          int32_t K, int64_t P, int32_t n_o, int32_t n_u, const float* obs0, const int32_t* step0,
+                          const float* obs, const float* term_obs, const float* u, const uint8_t* done, double dt,
+                          int32_t auto_reset, int32_t every, int64_t keep_last, hipStream_t stream) {
+    using DC = Dims<RCBF_MODE_SIMULATED_CARS, 1>;
+    using DU = Dims<RCBF_MODE_UNICYCLE, 1>;
+    const bool cars = n_o == DC::NO && n_u == DC::NU;
+    if (!cars && !(n_o == DU::NO && n_u == DU::NU)) return RCBF_E_BAD_SHAPE;
+    if (B < 0 || K <= 0 || P < B || every < 1 || keep_last < 1) return RCBF_E_BAD_SHAPE;
+    if (B == 0) return 0;
+    if (!state_out || !dist_out || !count_out || !scratch || !obs0 || !step0 || !obs || !u || !done)
+        return RCBF_E_NULL;
+    // a reset row as x' would be a garbage disturbance: no terminal rows, no auto-reset packing
+    if (auto_reset && !term_obs) return RCBF_E_NULL;
+    // cars rows are read as 8-byte pairs
+    if (cars && ((((uintptr_t)obs0) | ((uintptr_t)obs) | ((uintptr_t)term_obs)) & 7)) return RCBF_E_BAD_SHAPE;
+    if (((((uintptr_t)state_out) | ((uintptr_t)dist_out) | ((uintptr_t)count_out) | ((uintptr_t)scratch)) & 7) ||
+        B > INT32_MAX)
+        return RCBF_E_BAD_SHAPE;
+    const int64_t waves = (B + 63) / 64;
+    const int chunk = traj_steps_per_workgroup(waves, K);
+    const dim3 g((unsigned)waves, (unsigned)((K + chunk - 1) / chunk)), b(64);
+    int64_t* const offs = static_cast<int64_t*>(scratch);
+    hipLaunchKernelGGL(k_traj_gp_count, g, b, 0, stream, offs, B, (int)K, P, step0, done, (int)auto_reset, (int)every,
+                       chunk);
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(k_traj_gp_scan, dim3(1), dim3(1024), 0, stream, offs, waves * K, keep_last, count_out);
+    if (int e = launch_status()) return e;
+    if (cars)
+        hipLaunchKernelGGL((k_traj_pack_gp<RCBF_MODE_SIMULATED_CARS>), g, b, 0, stream, state_out, dist_out, offs,
+                           keep_last, B, (int)K, P, obs0, step0, obs, term_obs, u, done, dt, (int)auto_reset,
+                           (int)every, chunk);
+    else
+        hipLaunchKernelGGL((k_traj_pack_gp<RCBF_MODE_UNICYCLE>), g, b, 0, stream, state_out, dist_out, offs,
+                           keep_last, B, (int)K, P, obs0, step0, obs, term_obs, u, done, dt, (int)auto_reset,
+                           (int)every, chunk);
     return launch_status();
 }
 

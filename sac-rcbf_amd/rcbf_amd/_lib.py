@@ -23,7 +23,7 @@ SOLVER_PDIPM = 1
 SOLVER_GI = 2
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NONFINITE = 0, 1, 2, 3
 MAX_HAZARDS = 8
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _ERRORS = {1001: "RCBF_E_BAD_MODE", 1002: "RCBF_E_BAD_SHAPE", 1003: "RCBF_E_NULL", 1004: "RCBF_E_HSA",
            1005: "RCBF_E_TIMEOUT", 1006: "RCBF_E_GP_HANDOFF"}
@@ -134,6 +134,11 @@ SIGNATURES = {
     # step0, obs, term_obs, u, reward, done, max_episode_steps, dt, auto_reset, stream
     "rcbf_traj_pack_replay_f64": [_P, _I64, _I64, _I64, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32,
                                   ctypes.c_double, _I32, _P],
+    # a trajectory's selected transitions as GP dataset rows: state_out, dist_out, count_out, scratch, B, K, P, n_o,
+    # n_u, obs0, step0, obs, term_obs, u, done, dt, auto_reset, every, keep_last, stream
+    "rcbf_traj_pack_gp_f64": [_P, _P, _P, _P, _I64, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, ctypes.c_double,
+                              _I32, _I32, _I64, _P],
+    "rcbf_traj_pack_gp_scratch_bytes": [_I64, _I32],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],
@@ -167,6 +172,7 @@ def load():
         fn.restype = ctypes.c_int32
     lib.rcbf_version.restype = ctypes.c_char_p
     lib.rcbf_gp_workspace_floats.restype = ctypes.c_int64
+    lib.rcbf_traj_pack_gp_scratch_bytes.restype = ctypes.c_int64
     if lib.rcbf_abi_version() != ABI_VERSION or lib.rcbf_params_size() != ctypes.sizeof(RcbfParams):
         raise RuntimeError("librcbf_hip.so ABI mismatch (rebuild with `python __graft_entry__.py build`)")
     _bind_fast(lib)

@@ -6,6 +6,9 @@ or, once fitted, the GP posterior on the device (rcbf_amd.gp, the
 rcbf_gp_predict kernel), predict_next_state (:60-105; device tensors through
 the rcbf_predict_next_state kernel) and the disturbance
 history + GP fit (append_transition / fit_gp_model, :263-340).
+trajectory_rows / append_trajectory do what the training loop's
+append_transition per step does (main.py:110-113) for a whole trajectory plan
+(rcbf_amd.aql), the rows computed on the device (rcbf_traj_pack_gp_f64).
 
 Inside the fused step (rcbf_safe_step) get_state and the prior run in-kernel;
 this module serves the un-fused API: torch device tensors stay on device (no
@@ -106,6 +109,11 @@ class DynamicsModel:
         if expand and t is not None:
             t = t.reshape(1)
         disturbance = (nxt - x - self.env.dt * self._f_plus_gu(x, u, t)) / self.env.dt
+        self._append_rows(x, disturbance)
+
+    def _append_rows(self, x, disturbance):
+        """Rows (state, disturbance) into the ring, refitting where the
+        reference does."""
         # the reference's per-row loop (dynamics.py:263-290) as ring-buffer slices: rows are written in
         # chunks that end where the reference refits the GP (history_counter % (max / 10) == 0), so every
         # fit sees exactly the rows it does in the reference
@@ -124,6 +132,102 @@ class DynamicsModel:
             i += take
             if self.history_counter % every == 0:
                 self.fit_gp_model()
+
+    # -- a trajectory plan's transitions (main.py:110-113 for K steps x B envs) --
+    def trajectory_rows(self, env, traj, obs0, step0, rows=None, every=2, auto_reset=True, keep_last=None):
+        """The rows append_transition would store for the `rows` (default: all)
+        steps of a trajectory plan of `env` (AqlQueue.safe_step_plan(
+        trajectory=traj)), computed on the device (rcbf_traj_pack_gp_f64, no
+        intermediate tensor): the reference's loop (main.py:110-113) takes
+        state = get_state(obs), next_state = get_state(next_obs) on every
+        `every`-th episode step and appends (state, (next_state - state -
+        dt (f + g u)) / dt) with t the episode step x dt.  Returns (state,
+        disturbance, n_selected): two device fp64 tensors of shape (n, n_s)
+        in the order B envs stepped in lock-step make those calls (step-major),
+        n = min(n_selected, keep_last) -- the LAST keep_last selected rows,
+        what a ring of that size keeps.
+        obs0 (B, n_o) f32: the observation step 0 acted on; step0 (B,) i32:
+        env.step_count before the run; both cloned before plan.run().  traj
+        needs "obs", "u", "done" and, with auto_reset (as the plan ran),
+        "term_obs": the next state of a transition that ends an episode is
+        the terminal observation's, never the next episode's first."""
+        from . import _lib
+        from .replay_memory import check_trajectory
+        B, n_o, n_u = env.num_envs, env.n_o, env.n_u
+        dev = obs0.device if torch.is_tensor(obs0) else self.device
+        fields, K, pitch = check_trajectory("trajectory_rows", env, traj, ("obs", "u", "done"), obs0, step0, rows, dev)
+        if not auto_reset:
+            fields.pop("term_obs", None)
+        elif "term_obs" not in fields:
+            raise ValueError("trajectory_rows with auto_reset needs trajectory['term_obs']: the next state of a "
+                             "transition that ends an episode is the terminal observation's (record term_obs with "
+                             "the plan)")
+        every = int(every)
+        if every < 1:
+            raise ValueError(f"every must be at least 1, got {every}")
+        if keep_last is not None and int(keep_last) < 1:
+            raise ValueError(f"keep_last must be at least 1, got {keep_last}")
+        if (n_o, n_u) != (self._N_OBS[self.env.dynamics_mode], self.n_u):
+            raise ValueError(f"env rows {(n_o, n_u)} are not {self.env.dynamics_mode} rows")
+        if B == 0:  # nothing to select from: no launch
+            empty = torch.empty(2, 0, self.n_s, dtype=torch.float64, device=dev)
+            return empty[0], empty[1], 0
+        if dev.type != "cuda":
+            raise ValueError("trajectory_rows needs HIP device tensors")
+        n_max = B * (-(-K // every))  # no env selects more than ceil(K / every) steps
+        n_rows = n_max if keep_last is None else min(n_max, int(keep_last))
+        lib = _lib.load()
+        out = torch.empty(2, n_rows, self.n_s, dtype=torch.float64, device=dev)
+        count = torch.empty(2, dtype=torch.int64, device=dev)
+        scratch = torch.empty(lib.rcbf_traj_pack_gp_scratch_bytes(B, K) // 8, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.rcbf_traj_pack_gp_f64(
+                _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(count), _lib.ptr(scratch), B, K, pitch, n_o, n_u,
+                _lib.ptr(obs0), _lib.ptr(step0), _lib.ptr(fields["obs"]), _lib.ptr(fields.get("term_obs")),
+                _lib.ptr(fields["u"]), _lib.ptr(fields["done"]), float(self.env.dt), int(bool(auto_reset)), every,
+                n_rows, _lib.stream_of(dev))
+        _lib.check(rc, "rcbf_traj_pack_gp_f64")
+        n_sel, n = (int(v) for v in count.tolist())  # the one host read: the row count
+        return out[0, :n], out[1, :n], n_sel
+
+    def append_trajectory(self, env, traj, obs0, step0, rows=None, every=2, auto_reset=True, refit="every"):
+        """The reference loop's append_transition calls (main.py:110-113) for a
+        whole trajectory plan: trajectory_rows on the device, one copy to the
+        host, then the ring.  Arguments as trajectory_rows.  Returns the
+        number of transitions appended.
+        refit="every": ring, history_counter and every GP fit exactly as the
+        per-step append_transition calls leave them.  refit="last": only the
+        last max_history_count rows are computed and land in the slots
+        sequential appends would leave them in, history_counter advances by
+        the number selected, and the GP is fitted once at the end if a fit
+        point (history_counter % (max_history_count / 10) == 0) was crossed --
+        the form for B x K far above gp_model_size.  refit="none": the same,
+        never fitting.  (The reference's i_episode < gp_max_episodes gate is
+        the caller's: do not call.)"""
+        if refit not in ("every", "last", "none"):
+            raise ValueError(f"refit must be 'every', 'last' or 'none', got {refit!r}")
+        cap = self.max_history_count
+        state, dist, n_sel = self.trajectory_rows(env, traj, obs0, step0, rows=rows, every=every,
+                                                  auto_reset=auto_reset, keep_last=None if refit == "every" else cap)
+        x, d = state.cpu().numpy(), dist.cpu().numpy()
+        if refit == "every":
+            self._append_rows(x, d)
+            return n_sel
+        c0, m = self.history_counter, x.shape[0]
+        slots = (c0 + n_sel - m + np.arange(m)) % cap
+        self.disturbance_history["state"][slots] = x
+        self.disturbance_history["disturbance"][slots] = d
+        self.history_counter = c0 + n_sel
+        if refit == "last" and self._fit_point_in(c0, n_sel):
+            self.fit_gp_model()
+        return n_sel
+
+    def _fit_point_in(self, c0, n):
+        """Whether a counter value in (c0, c0 + n] triggers a fit."""
+        every = self.max_history_count / 10
+        if every == int(every) and every > 0:
+            return (c0 + n) // int(every) > c0 // int(every)
+        return any(c % every == 0 for c in range(c0 + 1, c0 + n + 1))
 
     def fit_gp_model(self, training_iter=70):
         from . import gp

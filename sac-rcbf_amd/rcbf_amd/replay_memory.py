@@ -28,6 +28,50 @@ import torch
 from . import _lib
 
 
+def check_trajectory(who, env, traj, needed, obs0, step0, rows, device):
+    """The argument checks of a consumer of a trajectory plan's arrays
+    (`who`: ReplayMemory.push_trajectory, DynamicsModel.trajectory_rows), made
+    before any library call: the `needed` fields and, when present, "term_obs"
+    are tensors of the dtype and shape env._trajectory_spec() gives, on
+    `device`, [:, :B] views of dense (K, P[, w]) arrays of one pitch P with at
+    least `rows` rows; obs0 (B, n_o) f32 and step0 (B,) i32 contiguous on
+    `device`.  Returns ({field: tensor}, K, pitch); raises ValueError."""
+    B, n_o = env.num_envs, env.n_o
+    for f in needed:
+        if f not in traj:
+            raise ValueError(f"{who} needs trajectory[{f!r}]")
+    spec = env._trajectory_spec()
+    fields = {f: traj[f] for f in (*needed, "term_obs") if traj.get(f) is not None}
+    K = min(int(t.shape[0]) for t in fields.values()) if rows is None else int(rows)
+    pitch = None
+    for f, t in fields.items():
+        w, dt = spec[f]
+        want = (B, w) if w else (B,)
+        if not (torch.is_tensor(t) and t.dtype == dt and t.device == device and t.dim() == len(want) + 1
+                and tuple(t.shape[1:]) == want):
+            raise ValueError(f"trajectory[{f!r}] must be a {dt} tensor of shape (K, {', '.join(map(str, want))}) "
+                             f"on {device}")
+        ww = w or 1
+        st = t.stride()
+        if st[1:] != ((w, 1) if w else (1,)) or st[0] % ww or st[0] // ww < B:
+            raise ValueError(f"trajectory[{f!r}] must be a [:, :B] view of a dense (K, P{', w' if w else ''}) "
+                             f"array (use env.make_trajectory), got strides {st}")
+        if pitch is not None and st[0] // ww != pitch:
+            raise ValueError(f"trajectory[{f!r}] has row pitch {st[0] // ww}, the other fields {pitch}")
+        pitch = st[0] // ww
+        if t.shape[0] < K:
+            raise ValueError(f"trajectory[{f!r}] has {t.shape[0]} rows, rows = {K}")
+    if K <= 0:
+        raise ValueError(f"rows must be positive, got {K}")
+    if not (torch.is_tensor(obs0) and obs0.dtype == torch.float32 and obs0.device == device
+            and tuple(obs0.shape) == (B, n_o) and obs0.is_contiguous()):
+        raise ValueError(f"obs0 must be a contiguous float32 tensor of shape ({B}, {n_o}) on {device}")
+    if not (torch.is_tensor(step0) and step0.dtype == torch.int32 and step0.device == device
+            and tuple(step0.shape) == (B,) and step0.is_contiguous()):
+        raise ValueError(f"step0 must be a contiguous int32 tensor of shape ({B},) on {device}")
+    return fields, K, pitch
+
+
 class ReplayMemory:
 
     def __init__(self, capacity, seed, device=None):
@@ -101,38 +145,8 @@ class ReplayMemory:
         first (warned about once).  mask, t and next_t follow main.py:100-107:
         mask 1 at the time limit, else 1 - done; t the episode step x dt."""
         B, n_o, n_u = env.num_envs, env.n_o, env.n_u
-        for f in ("obs", "u", "reward", "done"):
-            if f not in traj:
-                raise ValueError(f"push_trajectory needs trajectory[{f!r}]")
-        spec = env._trajectory_spec()
-        fields = {f: traj[f] for f in ("obs", "u", "reward", "done", "term_obs") if traj.get(f) is not None}
-        K = min(int(t.shape[0]) for t in fields.values()) if rows is None else int(rows)
-        pitch = None
-        for f, t in fields.items():
-            w, dt = spec[f]
-            want = (B, w) if w else (B,)
-            if not (torch.is_tensor(t) and t.dtype == dt and t.device == self.device and t.dim() == len(want) + 1
-                    and tuple(t.shape[1:]) == want):
-                raise ValueError(f"trajectory[{f!r}] must be a {dt} tensor of shape (K, {', '.join(map(str, want))}) "
-                                 f"on {self.device}")
-            ww = w or 1
-            st = t.stride()
-            if st[1:] != ((w, 1) if w else (1,)) or st[0] % ww or st[0] // ww < B:
-                raise ValueError(f"trajectory[{f!r}] must be a [:, :B] view of a dense (K, P{', w' if w else ''}) "
-                                 f"array (use env.make_trajectory), got strides {st}")
-            if pitch is not None and st[0] // ww != pitch:
-                raise ValueError(f"trajectory[{f!r}] has row pitch {st[0] // ww}, the other fields {pitch}")
-            pitch = st[0] // ww
-            if t.shape[0] < K:
-                raise ValueError(f"trajectory[{f!r}] has {t.shape[0]} rows, rows = {K}")
-        if K <= 0:
-            raise ValueError(f"rows must be positive, got {K}")
-        if not (torch.is_tensor(obs0) and obs0.dtype == torch.float32 and obs0.device == self.device
-                and tuple(obs0.shape) == (B, n_o) and obs0.is_contiguous()):
-            raise ValueError(f"obs0 must be a contiguous float32 tensor of shape ({B}, {n_o}) on {self.device}")
-        if not (torch.is_tensor(step0) and step0.dtype == torch.int32 and step0.device == self.device
-                and tuple(step0.shape) == (B,) and step0.is_contiguous()):
-            raise ValueError(f"step0 must be a contiguous int32 tensor of shape ({B},) on {self.device}")
+        fields, K, pitch = check_trajectory("push_trajectory", env, traj, ("obs", "u", "reward", "done"), obs0, step0,
+                                            rows, self.device)
         term = fields.get("term_obs")
         if term is None and auto_reset and not getattr(self, "_warned_no_term_obs", False):
             self._warned_no_term_obs = True
