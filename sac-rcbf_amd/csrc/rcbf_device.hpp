@@ -358,7 +358,12 @@ struct ActiveSet {
 // accumulation error does not survive.  Vertex case (|A| = n) solves
 // G_A z = h_A directly -- well conditioned after row normalisation even when
 // the multipliers are ~1e7 (Cascade unicycle, P = diag(10,1e-4,1e7)).
-template <int N, bool DIAG>
+// REFINE (the generic QP kernels, whose P is the caller's): for |A| < n one
+// more correction puts z back on the active rows.  z = x0 - P^-1 G_A' lam
+// cancels when |x0| >> |z| (a weak curvature, P_kk = 1e-4 against q = O(1)),
+// and leaves G_A z - h_A at ~|x0| eps; the correction solves S dlam = G_A z - h_A
+// and moves z and lam together, so stationarity is kept.
+template <int N, bool DIAG, bool REFINE = false>
 __device__ __forceinline__ void polish(const PMat<N, DIAG>& pm, const double* x0, const double* q,
                                        ActiveSet<N>& A, double* z) {
     if (A.n == N) {
@@ -422,6 +427,28 @@ __device__ __forceinline__ void polish(const PMat<N, DIAG>& pm, const double* x0
         for (int s = 0; s < N; ++s) acc -= PG[s][k] * lam[s];
         z[k] = acc;
     }
+    if constexpr (REFINE) {
+        double rr[N], dl[N];
+#pragma unroll
+        for (int s = 0; s < N; ++s) {
+            rr[s] = (s < A.n) ? dotd<N>(A.g[s], z) - A.h[s] : 0.0;
+#pragma unroll
+            for (int t = 0; t < N; ++t) S2[s][t] = S[s][t];
+        }
+        ldl_solve<N>(S2, rr, dl);
+#pragma unroll
+        for (int s = 0; s < N; ++s) {
+            dl[s] = (s < A.n) ? dl[s] : 0.0;
+            lam[s] += dl[s];
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            double acc = z[k];
+#pragma unroll
+            for (int s = 0; s < N; ++s) acc -= PG[s][k] * dl[s];
+            z[k] = acc;
+        }
+    }
 #pragma unroll
     for (int s = 0; s < N; ++s) A.lam[s] = lam[s];
 }
@@ -434,7 +461,7 @@ __device__ __forceinline__ void polish(const PMat<N, DIAG>& pm, const double* x0
 // Starting from the unconstrained minimum, the most violated row is added;
 // a partial step drops the blocking active row; every step keeps dual
 // feasibility, and the method terminates at the unique optimum.
-template <int N, int M, bool DIAG, typename R>
+template <int N, int M, bool DIAG, typename R, bool REFINE = false>
 __device__ __forceinline__ void gi_solve(const PMat<N, DIAG>& pm, const double* q, const R (*G)[N],
                                          const R* h, int max_iter, QPResult<N, M>& out) {
     double x0[N];
@@ -541,7 +568,11 @@ __device__ __forceinline__ void gi_solve(const PMat<N, DIAG>& pm, const double* 
                 break;
             }
             double t = fmin(t1, t2);
-            if (t2 != kInf) {
+            // REFINE (generic kernels): move on a partial step too when g_p is dependent on the active rows only
+            // to rounding (gz ~ -1e-16 after the fp32 normaliser moved a tight row by 1e-8: |zdir| ~ 1e-8, and with
+            // t = 9 the skipped move left x 1e-7 stale; a row it then violated by 1e-8 went unseen and the polish
+            // kept an active set one row short, z 1.5e-8 off).  For exactly dependent rows zdir is 0 to rounding.
+            if (REFINE || t2 != kInf) {
 #pragma unroll
                 for (int k = 0; k < N; ++k) x[k] = fma(t, zdir[k], x[k]);
             }
@@ -585,7 +616,62 @@ __device__ __forceinline__ void gi_solve(const PMat<N, DIAG>& pm, const double* 
         (void)added;
     }
     if (status == RCBF_QP_OK) {
-        polish<N, DIAG>(pm, x0, q, A, x);
+        polish<N, DIAG, REFINE>(pm, x0, q, A, x);
+        if constexpr (REFINE) {
+            // A tight row with a zero multiplier can end in the active set (it looked violated by the
+            // steps' rounding).  At a vertex the polish recomputes the multipliers from P z + q, where a
+            // heavy P_kk turns z_k's rounding into an error of P_kk eps: the zero multiplier comes out
+            // negative (-5e-10 at P_kk = 1e7).  Drop such a row and polish the rest; keep that point if
+            // it violates no row (it is the same optimum, now with multipliers >= 0), else the vertex.
+#pragma unroll
+            for (int rep = 0; rep < N; ++rep) {
+                int kd = -1;
+                double lmin = 0.0;
+#pragma unroll
+                for (int s = 0; s < N; ++s) {
+                    const bool neg = (s < A.n) && (A.lam[s] < lmin);
+                    lmin = neg ? A.lam[s] : lmin;
+                    kd = neg ? s : kd;
+                }
+                if (kd < 0) break;
+                ActiveSet<N> A2 = A;
+#pragma unroll
+                for (int s = 0; s + 1 < N; ++s) {
+                    const bool sh = (s >= kd);
+#pragma unroll
+                    for (int k = 0; k < N; ++k) A2.g[s][k] = sh ? A2.g[s + 1][k] : A2.g[s][k];
+                    A2.h[s] = sh ? A2.h[s + 1] : A2.h[s];
+                    A2.lam[s] = sh ? A2.lam[s + 1] : A2.lam[s];
+                    A2.idx[s] = sh ? A2.idx[s + 1] : A2.idx[s];
+                }
+                A2.n -= 1;
+                A2.idx[N - 1] = -1;
+                A2.lam[N - 1] = 0.0;
+#pragma unroll
+                for (int k = 0; k < N; ++k) A2.g[N - 1][k] = 0.0;
+                A2.h[N - 1] = 0.0;
+                double x2[N];
+                polish<N, DIAG, REFINE>(pm, x0, q, A2, x2);
+                bool keep = true;
+#pragma unroll
+                for (int r = 0; r < M; ++r) {
+                    double gr[N];
+#pragma unroll
+                    for (int k = 0; k < N; ++k) gr[k] = (double)G[r][k];
+                    keep = keep && (dotd<N>(gr, x2) - (double)h[r] <= 1e-11 * (1.0 + fabs((double)h[r])));
+                }
+#pragma unroll
+                for (int s = 0; s < N; ++s) keep = keep && (s >= A2.n || A2.lam[s] >= lmin);
+                if (!keep) break;
+                int dropped = A.idx[0];
+#pragma unroll
+                for (int s = 0; s < N; ++s) dropped = (s == kd) ? A.idx[s] : dropped;
+                amask &= ~(1u << dropped);
+                A = A2;
+#pragma unroll
+                for (int k = 0; k < N; ++k) x[k] = x2[k];
+            }
+        }
     }
     bool okf = true;
 #pragma unroll
@@ -616,7 +702,7 @@ __device__ __forceinline__ void gi_solve(const PMat<N, DIAG>& pm, const double* 
 // stop rule (resid < eps, or notImprovedLim steps without improvement).
 // Followed by the same exact active-set polish as the GI path (rows with
 // lam > s), so the returned z is the KKT point of the identified set.
-template <int N, int M, bool DIAG, typename R>
+template <int N, int M, bool DIAG, typename R, bool REFINE = false>
 __device__ __forceinline__ void pdipm_solve(const PMat<N, DIAG>& pm, const double* q, const R (*G)[N],
                                             const R* h, int max_iter, double eps, QPResult<N, M>& out) {
     double Gd[M][N], hd[M];
@@ -867,13 +953,57 @@ __device__ __forceinline__ void pdipm_solve(const PMat<N, DIAG>& pm, const doubl
 #pragma unroll
         for (int k = 0; k < N; ++k) x0[k] = -x0[k];
         double zp[N];
-        polish<N, DIAG>(pm, x0, q, A, zp);
-        // accept the polish only if it is primal and dual feasible
+        polish<N, DIAG, REFINE>(pm, x0, q, A, zp);
+        // accept the polish only if it is a KKT point: primal and dual feasible
+        // and stationary.  The picked rows can be dependent (both sides of a
+        // thin slab): the vertex solve is then singular, z runs off along the
+        // slab (still feasible) and the multipliers are +inf, which pass a
+        // sign test; the stationarity residual (NaN or inf then) does not.
         bool ok = true;
+        // (generic kernels: to Goldfarb-Idnani's own row tolerance, so that the fp64 solution holds 1e-9)
 #pragma unroll
-        for (int r = 0; r < M; ++r) ok = ok && (dotd<N>(Gd[r], zp) - hd[r] <= 1e-9 * (1.0 + fabs(hd[r])));
+        for (int r = 0; r < M; ++r)
+            ok = ok && (dotd<N>(Gd[r], zp) - hd[r] <= (REFINE ? 1e-12 : 1e-9) * (1.0 + fabs(hd[r])));
+        double lsc = 1.0;
 #pragma unroll
-        for (int sl = 0; sl < N; ++sl) ok = ok && (sl >= A.n || A.lam[sl] >= -1e-9);
+        for (int sl = 0; sl < N; ++sl) lsc = fmax(lsc, (sl < A.n) ? fabs(A.lam[sl]) : 0.0);
+#pragma unroll
+        for (int sl = 0; sl < N; ++sl) ok = ok && (sl >= A.n || A.lam[sl] >= -1e-14 * lsc);
+        // the picked rows must be independent: LDL^T pivots of their Gram matrix against its diagonal
+        // (sin^2 of the angle to the rows before); two sides of a slab give 0 up to rounding
+        {
+            double Lg[N][N], Dg[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const double gjj = (j < A.n) ? dotd<N>(A.g[j], A.g[j]) : 1.0;
+                double dd = gjj;
+#pragma unroll
+                for (int k = 0; k < j; ++k) dd -= Lg[j][k] * Lg[j][k] * Dg[k];
+                ok = ok && (dd > 1e-12 * gjj);
+                Dg[j] = dd;
+                const double inv = rcp64(dd);
+#pragma unroll
+                for (int i = j + 1; i < N; ++i) {
+                    double v = (i < A.n && j < A.n) ? dotd<N>(A.g[i], A.g[j]) : 0.0;
+#pragma unroll
+                    for (int k = 0; k < j; ++k) v -= Lg[i][k] * Lg[j][k] * Dg[k];
+                    Lg[i][j] = v * inv;
+                }
+            }
+        }
+        double Pz[N];
+        pm.apply(zp, Pz);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            double acc = Pz[k] + q[k], sc = fabs(Pz[k]) + fabs(q[k]);
+#pragma unroll
+            for (int sl = 0; sl < N; ++sl) {
+                const double t = (sl < A.n) ? A.g[sl][k] * A.lam[sl] : 0.0;
+                acc += t;
+                sc += fabs(t);
+            }
+            ok = ok && (fabs(acc) <= 1e-9 * (1.0 + sc));
+        }
 #pragma unroll
         for (int k = 0; k < N; ++k) z[k] = ok ? zp[k] : z[k];
         out.certified = ok;
@@ -1605,23 +1735,23 @@ __device__ __forceinline__ void uni_qp_2d_raw(const PMat<3, true>& pm, const R (
 //                           for n = 3 or a full P;
 //   RCBF_SOLVER_GI:         Goldfarb-Idnani for every size;
 //   RCBF_SOLVER_PDIPM:      primal-dual interior point + active-set polish.
-template <int SOLVER, int N, int M, bool DIAG, typename R>
+template <int SOLVER, int N, int M, bool DIAG, typename R, bool REFINE = false>
 __device__ __forceinline__ void qp_solve(const PMat<N, DIAG>& pm, const double* q, const R (*G)[N],
                                          const R* h, int max_iter, double eps, QPResult<N, M>& out) {
     if constexpr (SOLVER == RCBF_SOLVER_PDIPM) {
-        pdipm_solve<N, M, DIAG, R>(pm, q, G, h, max_iter > 0 ? max_iter : 50, eps > 0 ? eps : 1e-10, out);
+        pdipm_solve<N, M, DIAG, R, REFINE>(pm, q, G, h, max_iter > 0 ? max_iter : 50, eps > 0 ? eps : 1e-10, out);
         // qpth returns its best iterate when it stalls (notImprovedLim), which
         // can be far from the optimum on badly scaled rows; a point that fails
         // the KKT certificate is re-solved exactly instead (rare lanes only).
         if (!out.certified && out.status != RCBF_QP_NONFINITE) {
             const int its = out.iters;
-            gi_solve<N, M, DIAG, R>(pm, q, G, h, 4 * (M + N) + 8, out);
+            gi_solve<N, M, DIAG, R, REFINE>(pm, q, G, h, 4 * (M + N) + 8, out);
             out.iters = its;
         }
     } else if constexpr (SOLVER == RCBF_SOLVER_ACTIVE_SET && N == 2 && DIAG) {
         enum2_solve_fast<M, R>(pm, G, h, out);
     } else {
-        gi_solve<N, M, DIAG, R>(pm, q, G, h, max_iter > 0 ? max_iter : 4 * (M + N) + 8, out);
+        gi_solve<N, M, DIAG, R, REFINE>(pm, q, G, h, max_iter > 0 ? max_iter : 4 * (M + N) + 8, out);
     }
 }
 

@@ -162,14 +162,14 @@ __global__ void __launch_bounds__(kQPBlock) k_qp_bwd(rcbf_params prm, int64_t B,
             }
         }
         if (need_gi) {
-            gi_solve<N, MP, true, float>(pm, Q.q, Q.G, Q.h, 4 * (MP + N) + 8, res);
+            gi_solve<N, MP, true, float, true>(pm, Q.q, Q.G, Q.h, 4 * (MP + N) + 8, res);  // REFINE, as the forward
             qp_adjoint<N, MP, true>(pm, Q, g, res, dz, eta, aidx);
         }
     } else if (active) {
         PMat<N, false> pm;
         pmat_set_full<N>(pm, Q.P);
         if (!gi_solve_chol<N, MP, float>(Q, 4 * (MP + N) + 8, res))
-            gi_solve<N, MP, false, float>(pm, Q.q, Q.G, Q.h, 4 * (MP + N) + 8, res);
+            gi_solve<N, MP, false, float, true>(pm, Q.q, Q.G, Q.h, 4 * (MP + N) + 8, res);
         qp_adjoint<N, MP, false>(pm, Q, g, res, dz, eta, aidx);
     }
     __syncthreads();  // every lane is done reading the staged inputs: the buffers now carry the gradients

@@ -282,7 +282,7 @@ __device__ __forceinline__ bool gi_solve_chol(const StagedQP<N, MP, T>& Q, int m
 #pragma unroll
     for (int k = 0; k < N; ++k) one[k] = 1.0;
     pmat_set_diag<N>(pm, one);
-    gi_solve<N, MP, true, double>(pm, qy, Gy, hy, max_iter, res);
+    gi_solve<N, MP, true, double, true>(pm, qy, Gy, hy, max_iter, res);
     double z[N];
 #pragma unroll
     for (int a = N - 1; a >= 0; --a) {  // z = L^-T y
@@ -512,7 +512,7 @@ __global__ void __launch_bounds__(kQPBlock) k_qp_solve(rcbf_params prm, int64_t 
 #pragma unroll
             for (int k = 0; k < N; ++k) pd[k] = Q.P[k][k];
             pmat_set_diag_rt<N>(pm, pd);
-            qp_solve<SOLVER, N, MP, true, T>(pm, Q.q, Q.G, Q.h, prm.max_iter, prm.eps, res);
+            qp_solve<SOLVER, N, MP, true, T, true>(pm, Q.q, Q.G, Q.h, prm.max_iter, prm.eps, res);
         } else {
             bool done = false;
             if constexpr (SOLVER != RCBF_SOLVER_PDIPM)
@@ -520,7 +520,7 @@ __global__ void __launch_bounds__(kQPBlock) k_qp_solve(rcbf_params prm, int64_t 
             if (!done) {
                 PMat<N, false> pm;
                 pmat_set_full<N>(pm, Q.P);
-                qp_solve<SOLVER, N, MP, false, T>(pm, Q.q, Q.G, Q.h, prm.max_iter, prm.eps, res);
+                qp_solve<SOLVER, N, MP, false, T, true>(pm, Q.q, Q.G, Q.h, prm.max_iter, prm.eps, res);
             }
         }
     }
@@ -531,9 +531,16 @@ __global__ void __launch_bounds__(kQPBlock) k_qp_solve(rcbf_params prm, int64_t 
         for (int k = 0; k < N; ++k) z64_out[i * N + k] = res.z[k];
     }
     if (lam_out) {
+        double lsc = 1.0;
 #pragma unroll
-        for (int r = 0; r < MP; ++r)
-            if (r < m) lam_out[i * m + r] = res.lam[r];
+        for (int r = 0; r < MP; ++r) lsc = fmax(lsc, fabs(res.lam[r]));
+        // a zero multiplier recomputed on a degenerate active set comes out as -1e-16: report 0.  Only
+        // rounding is zeroed (above -1e-12 max(1, |lam|)); a really negative multiplier, or a NaN, stays.
+#pragma unroll
+        for (int r = 0; r < MP; ++r) {
+            const double l = res.lam[r];
+            if (r < m) lam_out[i * m + r] = (l < 0.0 && l >= -1e-12 * lsc) ? 0.0 : l;
+        }
     }
     report(res.status, status_out, i, fail_flag);
 }
