@@ -437,6 +437,48 @@ int rcbf_traj_pack_gp_f64(double* state_out, double* dist_out, int64_t* count_ou
                           const float* obs, const float* term_obs, const float* u, const uint8_t* done, double dt,
                           int32_t auto_reset, int32_t every, int64_t keep_last, hipStream_t stream);
 
+/* The episode bookkeeping of the reference's loop over the steps of a
+ * trajectory plan: episode_reward += reward, episode_cost += info['cost'],
+ * episode_steps += 1 per step (main.py:98-101) and the (steps, reward, cost)
+ * an episode that ends logs (main.py:140-144; the same again in main.py:152-170
+ * and rcbf_sac/evaluator.py:33-54), as five dense arrays of one record per
+ * finished episode plus each env's running sums.  Three launches on `stream`
+ * (count, scan, pack), no host synchronisation, no atomics: the result is the
+ * same in every run.
+ * reward, cost [nullable]: (K, P) f32 with pitch P >= B envs; done (K, P) u8.
+ * carry_in [nullable]: (B, 2) f64, each env's (return, cost) so far; len_in
+ * [nullable]: (B,) i32, its episode-step count; null means zeros.  For env i,
+ * with R = carry_in[i][0], C = carry_in[i][1], c = len_in[i], for j = 0 .. K-1
+ * in this order:
+ *   R = R + (double)reward[j][i]
+ *   C = C + (double)cost[j][i]            (skipped if cost is null)
+ *   e = c + 1
+ *   if done[j][i] and auto_reset: an episode ends here, with the record
+ *     (env i, step j, length e, return R, cost C); then R = C = 0, c = 0
+ *   else c = e
+ * (the recurrence of rcbf_traj_pack_replay_f64; with auto_reset == 0 nothing
+ * ends and the sums run through done).  All fp64: fp32 widens exactly and the
+ * additions are made in step order, so every output is bit-reproducible from
+ * the inputs.
+ * The n_ep episodes are numbered step-major, env-minor (the order in which B
+ * envs stepped in lock-step would log them).  rows = min(n_ep, max_rows)
+ * records are written: record r < rows at index r of ep_env, ep_step, ep_len
+ * (i32) and ep_return, ep_cost (f64), each (max_rows,) -- the FIRST max_rows.
+ * Nothing outside [0, rows) is written.  count_out: int64[2] on the device =
+ * {n_ep, rows}, so a caller sees truncation.  After the K steps (R, C) goes to
+ * carry_out[i] and c to len_out[i], each if non-null.
+ * max_rows == 0 is the count-only call: the five record arrays may be null.
+ * carry_in / carry_out 16-byte aligned, and carry_out must not overlap
+ * carry_in nor len_out len_in (RCBF_E_BAD_SHAPE): in and out are separate
+ * arrays.  scratch: caller-owned, rcbf_traj_episode_stats_scratch_bytes(B, K)
+ * bytes, 8-byte aligned, contents undefined before and after. */
+int64_t rcbf_traj_episode_stats_scratch_bytes(int64_t B, int32_t K);
+int rcbf_traj_episode_stats_f64(int32_t* ep_env, int32_t* ep_step, int32_t* ep_len, double* ep_return,
+                                double* ep_cost, int64_t* count_out, void* scratch, int64_t B, int32_t K, int64_t P,
+                                const float* reward, const float* cost, const uint8_t* done, const double* carry_in,
+                                const int32_t* len_in, double* carry_out, int32_t* len_out, int32_t auto_reset,
+                                int64_t max_rows, hipStream_t stream);
+
 /* ReplayMemory.sample (replay_memory.py:31-35) gather: dst[r] = ring[idx[r]]. */
 int rcbf_gather_rows_f64(double* dst, const double* ring, int64_t W, const int64_t* idx,
                          int64_t n, hipStream_t stream);

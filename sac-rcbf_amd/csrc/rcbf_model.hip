@@ -693,6 +693,144 @@ inline int traj_steps_per_workgroup(int64_t waves, int K) {
     return (int)((K + parts - 1) / parts);
 }
 
+// rcbf_traj_episode_stats_f64: the reference loop's episode bookkeeping (main.py:98-101: episode_reward +=
+// reward, episode_cost += info['cost'], episode_steps += 1; :140-144: the line an episode that ends logs) over
+// the (K, P) reward, cost and done arrays of a trajectory plan.  Which (step, env) pairs end an episode depends
+// on the done bytes alone, so the work is the three launches of the GP packer: k_traj_ep_count (the lanes of
+// each (step, wave) that end one, from a ballot), k_traj_gp_scan as it stands (their exclusive prefix sum,
+// step-major, wave-minor: the record index of every wave's first episode of every step) and k_traj_ep_pack.
+
+// counts[j waves + w] = envs of wave w whose episode ends at step j.  No state runs from step to step (a done
+// byte ends an episode whatever the sums are), so blockIdx.y's chunk of steps starts cold; 8 steps' bytes are in
+// flight together, as in k_traj_gp_count.
+__global__ void __launch_bounds__(64) k_traj_ep_count(int64_t* __restrict__ counts, int64_t B, int K, int64_t P,
+                                                      const uint8_t* __restrict__ done, int auto_reset, int chunk) {
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = i < B;
+    const int j0 = (int)blockIdx.y * chunk;
+    const int j1 = j0 + chunk < K ? j0 + chunk : K;
+    for (int j = j0; j < j1; j += 8) {
+        uint8_t b[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = (live && j + k < j1) ? ld_in(&done[(int64_t)(j + k) * P + i]) : 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (j + k < j1) {  // (wave-uniform)
+                const unsigned long long m = __ballot(b[k] != 0 && auto_reset);
+                if (lane == 0) counts[(int64_t)(j + k) * gridDim.x + blockIdx.x] = (int64_t)__popcll(m);
+            }
+        }
+    }
+}
+
+// kEpSteps steps of one env's reward, cost and done from step j on: row-coalesced `nt` loads (a wave's 64
+// values of a step are one run of memory), all issued before any is used, and none of them conditional: a lane
+// past B loads env B - 1's values and a step past K step K - 1's (the same lines again), to be ignored.
+constexpr int kEpSteps = 8;
+template <bool COST>
+struct EpisodeBlock {
+    float rw[kEpSteps], cs[kEpSteps];
+    uint8_t dn[kEpSteps];
+    __device__ __forceinline__ void load(const float* __restrict__ reward, const float* __restrict__ cost,
+                                         const uint8_t* __restrict__ done, int64_t P, int64_t i, int j, int K) {
+#pragma unroll
+        for (int k = 0; k < kEpSteps; ++k) {
+            const int64_t e = (int64_t)(j + k < K ? j + k : K - 1) * P + i;
+            rw[k] = ld_in(&reward[e]);
+            if constexpr (COST) cs[k] = ld_in(&cost[e]);
+            dn[k] = ld_in(&done[e]);
+        }
+    }
+};
+
+// The pack pass.  One env per lane, a wave per workgroup, the lane carrying its env's return R, cost C and
+// episode-step count c in registers over all K steps (each is the sum of everything before it: the additions
+// are made in step order, fp32 widened exactly, so every output is bit-reproducible from the inputs).  The
+// loads run a block of kEpSteps steps ahead of the adds: the next block's are issued before this block's first
+// value is used, so a lane waits for a load round trip once per block at the most, not once per step.  At a step
+// where lanes end an episode they are ranked by a ballot; the lane of rank q owns record offs[j waves + w] + q
+// and stores its five values there if that is below max_rows -- the stores of one field from one wave and step
+// are one contiguous run.  Episode ends are sparse: plain per-lane stores, no LDS staging.
+template <bool COST>
+__global__ void __launch_bounds__(64) k_traj_ep_pack(int32_t* __restrict__ ep_env, int32_t* __restrict__ ep_step,
+                                                     int32_t* __restrict__ ep_len, double* __restrict__ ep_return,
+                                                     double* __restrict__ ep_cost, const int64_t* __restrict__ offs,
+                                                     int64_t max_rows, int64_t B, int K, int64_t P,
+                                                     const float* __restrict__ reward,
+                                                     const float* __restrict__ cost,
+                                                     const uint8_t* __restrict__ done,
+                                                     const double* __restrict__ carry_in,
+                                                     const int32_t* __restrict__ len_in,
+                                                     double* __restrict__ carry_out, int32_t* __restrict__ len_out,
+                                                     int auto_reset) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const int lane = threadIdx.x;
+    const int64_t w = blockIdx.x, waves = gridDim.x;
+    const int64_t i = w * 64 + lane;
+    const bool live = i < B;
+    const int64_t il = live ? i : B - 1;  // the env whose values this lane loads
+    const bool on = live && auto_reset;   // this lane's done bytes end episodes
+    double R = 0.0, C = 0.0;
+    int c = 0;
+    if (carry_in) {  // (the oldest loads: complete when the first block's are)
+        const double2 v = ld_in2(carry_in + 2 * il);
+        R = v.x;
+        C = v.y;
+    }
+    if (len_in) c = ld_in(&len_in[il]);
+    // the steps [j, j + kEpSteps) below K, their values in `blk`
+    auto walk = [&](const EpisodeBlock<COST>& blk, int j) {
+#pragma unroll
+        for (int k = 0; k < kEpSteps; ++k) {
+            if (j + k >= K) break;  // (wave-uniform)
+            R = R + (double)blk.rw[k];
+            if constexpr (COST) C = C + (double)blk.cs[k];
+            const int e = c + 1;
+            const bool end = (blk.dn[k] != 0) & on;
+            const unsigned long long m = __ballot(end);
+            if (end) {
+                const int q =
+                    (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                const int64_t slot = offs[(int64_t)(j + k) * waves + w] + q;
+                if (slot < max_rows) {
+                    ep_env[slot] = (int32_t)i;
+                    ep_step[slot] = j + k;
+                    ep_len[slot] = e;
+                    ep_return[slot] = R;
+                    ep_cost[slot] = C;
+                }
+            }
+            R = end ? 0.0 : R;
+            C = end ? 0.0 : C;
+            c = end ? 0 : e;
+        }
+    };
+    // two blocks in turn, each reloaded as soon as it is walked: no copy between them, and a load is never
+    // conditional (past K it repeats row K - 1), so the wait before a block's first value leaves the other
+    // block's loads in flight
+    EpisodeBlock<COST> a, b;
+    a.load(reward, cost, done, P, il, 0, K);
+    for (int j = 0; j < K; j += 2 * kEpSteps) {
+        b.load(reward, cost, done, P, il, j + kEpSteps, K);
+        walk(a, j);
+        a.load(reward, cost, done, P, il, j + 2 * kEpSteps, K);
+        walk(b, j + kEpSteps);
+    }
+    if (live && carry_out) {
+        const d2 v = {R, C};
+        __builtin_nontemporal_store(v, reinterpret_cast<d2*>(carry_out + 2 * i));
+    }
+    if (live && len_out) len_out[i] = c;
+}
+
+// [a, a + bytes) and [b, b + bytes) share a byte (null: no)
+inline bool ranges_overlap(const void* a, const void* b, int64_t bytes) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
+}
+
 }  // namespace
 
 // DynamicsModel.get_state on fp32 observation rows (dynamics.py:190-232): the
@@ -845,6 +983,49 @@ int rcbf_traj_pack_gp_f64(double* state_out, double* dist_out, int64_t* count_ou
         hipLaunchKernelGGL((k_traj_pack_gp<RCBF_MODE_UNICYCLE>), g, b, 0, stream, state_out, dist_out, offs,
                            keep_last, B, (int)K, P, obs0, step0, obs, term_obs, u, done, dt, (int)auto_reset,
                            (int)every, chunk);
+    return launch_status();
+}
+
+int64_t rcbf_traj_episode_stats_scratch_bytes(int64_t B, int32_t K) {
+    if (B < 0 || K <= 0) return 0;
+    return 8 * (((B + 63) / 64) * (int64_t)K + 1);  // a count per (step, wave), and the total
+}
+
+int rcbf_traj_episode_stats_f64(int32_t* ep_env, int32_t* ep_step, int32_t* ep_len, double* ep_return,
+                                double* ep_cost, int64_t* count_out, void* scratch, int64_t B, int32_t K, int64_t P,
+                                const float* reward, const float* cost, const uint8_t* done, const double* carry_in,
+                                const int32_t* len_in, double* carry_out, int32_t* len_out, int32_t auto_reset,
+                                int64_t max_rows, hipStream_t stream) {
+    if (B < 0 || K <= 0 || P < B || max_rows < 0 || B > INT32_MAX) return RCBF_E_BAD_SHAPE;
+    if (B == 0) return 0;
+    if (!reward || !done || !count_out || !scratch) return RCBF_E_NULL;
+    if (max_rows > 0 && (!ep_env || !ep_step || !ep_len || !ep_return || !ep_cost)) return RCBF_E_NULL;
+    auto at = [](const void* p) { return (uintptr_t)p; };
+    if ((at(carry_in) | at(carry_out)) & 15) return RCBF_E_BAD_SHAPE;  // a lane's (R, C) is one 16-byte access
+    if ((at(ep_return) | at(ep_cost) | at(count_out) | at(scratch)) & 7) return RCBF_E_BAD_SHAPE;
+    if ((at(ep_env) | at(ep_step) | at(ep_len) | at(reward) | at(cost) | at(len_in) | at(len_out)) & 3)
+        return RCBF_E_BAD_SHAPE;
+    // in and out are separate arrays: a lane reads its carry where another call's lane may be writing its own
+    if (ranges_overlap(carry_in, carry_out, 16 * B) || ranges_overlap(len_in, len_out, 4 * B)) return RCBF_E_BAD_SHAPE;
+    const int64_t waves = (B + 63) / 64;
+    const int chunk = traj_steps_per_workgroup(waves, K);
+    int64_t* const offs = static_cast<int64_t*>(scratch);
+    hipLaunchKernelGGL(k_traj_ep_count, dim3((unsigned)waves, (unsigned)((K + chunk - 1) / chunk)), dim3(64), 0, stream,
+                       offs, B, (int)K, P, done, (int)auto_reset, chunk);
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(k_traj_gp_scan, dim3(1), dim3(1024), 0, stream, offs, waves * K, max_rows, count_out);
+    if (int e = launch_status()) return e;
+    if (max_rows == 0 && !carry_out && !len_out) return 0;  // the count-only call: the pack pass would write nothing
+    // the pack pass: a lane walks all K steps of its env (the sums are serial); no split over the steps
+    const dim3 g((unsigned)waves), b(64);
+    if (cost)
+        hipLaunchKernelGGL((k_traj_ep_pack<true>), g, b, 0, stream, ep_env, ep_step, ep_len, ep_return, ep_cost, offs,
+                           max_rows, B, (int)K, P, reward, cost, done, carry_in, len_in, carry_out, len_out,
+                           (int)auto_reset);
+    else
+        hipLaunchKernelGGL((k_traj_ep_pack<false>), g, b, 0, stream, ep_env, ep_step, ep_len, ep_return, ep_cost, offs,
+                           max_rows, B, (int)K, P, reward, cost, done, carry_in, len_in, carry_out, len_out,
+                           (int)auto_reset);
     return launch_status();
 }
 

@@ -10,7 +10,9 @@ safety-layer QP, as hand-written HIP kernels for gfx950 behind a C-ABI
   rcbf_amd.envs.SimulatedCarsEnv / UnicycleEnv   <- envs/*_env.py
   rcbf_amd.envs.Batched*Env (+ safe_step / rollout: the fused kernels)
   rcbf_amd.build_env.build_env          <- build_env.py
+  rcbf_amd.EpisodeStats (episode_stats) <- main.py:98-101,140-144, the loop's episode bookkeeping
 """
 from . import _lib  # noqa: F401
+from .episode_stats import EpisodeStats  # noqa: F401
 
 __version__ = "0.1.0"

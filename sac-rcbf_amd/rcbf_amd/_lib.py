@@ -139,6 +139,11 @@ SIGNATURES = {
     "rcbf_traj_pack_gp_f64": [_P, _P, _P, _P, _I64, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, ctypes.c_double,
                               _I32, _I32, _I64, _P],
     "rcbf_traj_pack_gp_scratch_bytes": [_I64, _I32],
+    # a trajectory's finished episodes and running sums: ep_env, ep_step, ep_len, ep_return, ep_cost, count_out,
+    # scratch, B, K, P, reward, cost, done, carry_in, len_in, carry_out, len_out, auto_reset, max_rows, stream
+    "rcbf_traj_episode_stats_f64": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _I32,
+                                    _I64, _P],
+    "rcbf_traj_episode_stats_scratch_bytes": [_I64, _I32],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],
@@ -173,6 +178,7 @@ def load():
     lib.rcbf_version.restype = ctypes.c_char_p
     lib.rcbf_gp_workspace_floats.restype = ctypes.c_int64
     lib.rcbf_traj_pack_gp_scratch_bytes.restype = ctypes.c_int64
+    lib.rcbf_traj_episode_stats_scratch_bytes.restype = ctypes.c_int64
     if lib.rcbf_abi_version() != ABI_VERSION or lib.rcbf_params_size() != ctypes.sizeof(RcbfParams):
         raise RuntimeError("librcbf_hip.so ABI mismatch (rebuild with `python __graft_entry__.py build`)")
     _bind_fast(lib)
