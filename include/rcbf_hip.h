@@ -209,7 +209,9 @@ int rcbf_safe_action_apply_jac(int64_t B, int32_t n_u, const double* jac, const 
  * normalise -> exact QP.  Returns u_qp only (caller adds u_nom, no clamp);
  * eps_out [nullable] (B,) f64 receives the slack epsilon, the QP solution's
  * last component (sol[0][-1], which the reference checks against 0.1 at
- * cbf_qp.py:283-284). */
+ * cbf_qp.py:283-284).  A sample whose rows are not finite (a NaN state)
+ * reports RCBF_QP_NONFINITE and NaN in u_safe_out and eps_out, with every
+ * solver. */
 int rcbf_cascade_u_safe(const rcbf_params* prm, int64_t B, const double* u_nom,
                         const double* x, const double* mu, const double* sigma,
                         double* u_safe_out, int32_t* status_out, int32_t* fail_flag,

@@ -41,6 +41,11 @@ __device__ __forceinline__ void cascade_one(const rcbf_params& prm, int64_t i, c
         uni_qp_2d<K, double>(pm, G, h, res.z, res.status);
     else
         qp_solve<SOLVER, D::N, D::M, true, double>(pm, q, G, h, prm.max_iter, prm.eps, res);
+    // non-finite rows have no solution: NaN from every solver (Goldfarb-Idnani stops on its start point, z = -0)
+    if (res.status == RCBF_QP_NONFINITE) {
+#pragma unroll
+        for (int k = 0; k < D::N; ++k) res.z[k] = __builtin_nan("");
+    }
 #pragma unroll
     for (int c = 0; c < D::NU; ++c) u_out[i * D::NU + c] = res.z[c];
     if (eps_out) eps_out[i] = res.z[D::NU];  // the slack, sol[0][-1] (cbf_qp.py:278, 283-284)
