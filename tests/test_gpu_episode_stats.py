@@ -286,3 +286,45 @@ def test_a_real_cars_plan_ends_one_episode_of_300_steps_per_env():
     run, steps = stats.running()
     assert np.array_equal(bits(run.cpu().numpy()), bits(carry))
     assert torch.equal(steps, env.step_count) and np.all(length == K - 300)
+
+
+@pytest.fixture
+def _large_shapes_leave_the_caches():
+    """The inputs and the oracle's records of a large shape are not kept for
+    the rest of the session."""
+    yield
+    _inputs.cache_clear()
+    _oracle.cache_clear()
+
+
+@pytest.mark.parametrize("B,P,K", [(8256, 8320, 40), (8224, 8320, 40), (65600, 65664, 19)])
+def test_several_steps_per_workgroup_equal_the_loop(B, P, K, _large_shapes_leave_the_caches):
+    """GRID gives every workgroup of the count pass ONE step (waves x K is far
+    below 8 waves per CU), so only lane 0 of its 8-step batch ever holds a live
+    step.  (8 256, 40): chunks of 3 steps on a 256-CU device, the last of 1.
+    (8 224, 40): the same grid with a last wave of 32 envs beside the NaN /
+    done = 1 padding (8 256 and 65 600 are multiples of 64).  (65 600, 19), the
+    grid training runs: chunks of 10 and 9 steps -- a full batch of 8 and a
+    tail -- and 1 025 x 19 = 19 475 counts, two tiles of the scan.  The full
+    call with carries in and out, and max_rows at half the episodes and inside
+    the last wave's records of a step in the middle of a chunk."""
+    from _traj_grid import chunk as grid_chunk
+    chunk, waves = grid_chunk(B, K), (B + 63) // 64
+    assert 1 < chunk < K
+    if K == 40:
+        assert chunk < 8 and K % chunk  # a partly filled batch; a shorter last chunk
+        assert B % 64 == (32 if B == 8224 else 0)
+    else:
+        assert chunk > 8 and chunk % 8 and waves * K > 16384
+    want, carry, length = _oracle(B, K)
+    n_ep = want["env"].size
+    assert n_ep == _inputs(B, K)["done"].sum() > K * B // 4
+    _check(*_run(B, P, K), want, carry, length)
+    j = chunk + chunk // 2  # a step that is neither its chunk's first nor its last
+    assert 0 < j % chunk < chunk - 1 and j < K
+    here = np.nonzero((want["step"] == j) & (want["env"] // 64 == waves - 1))[0]
+    assert here.size >= 2 and np.array_equal(here, np.arange(here[0], here[0] + here.size))
+    inside = int(here[0]) + here.size // 2
+    assert here[0] < inside <= here[-1]
+    for max_rows in (n_ep // 2, inside):
+        _check(*_run(B, P, K, max_rows=max_rows), want, carry, length, max_rows=max_rows)

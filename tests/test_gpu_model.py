@@ -270,3 +270,208 @@ def test_predict_next_state_staged_rows_ragged_and_unaligned():
     nx, sd, _ = dm.predict_next_state(buf[1:].view(B, 10), ud, t_batch=td, use_gps=True)
     assert np.array_equal(nx.cpu().numpy(), outs[0] + 0.02 * m32.astype(np.float64))
     assert np.array_equal(sd.cpu().numpy(), 0.02 * s32.astype(np.float64))
+
+
+# ----------------------------------------------------------------------------
+# rcbf_model_step: every in-kernel draw against the oracle's keyed draw, and
+# the output branches against oracle.model_rollout_step
+# ----------------------------------------------------------------------------
+DRAW_TOL = 2e-5                 # hardware fp32 log2 / cos / sin against numpy's: test_model_step_draw_moments_tails_and_key
+DRAW_B = 65536 + 77             # a ragged last workgroup
+DRAW_SEED = (7 << 32) | 11      # the key's high word is live
+CARS_X0 = np.array([34.0, 30.0, 28.0, 30.0, 22.0, 30.0, 16.0, 35.0, 10.0, 30.0])
+
+
+def _cars_rows(rng, B):
+    obs = np.tile(CARS_X0, (B, 1)) + rng.normal(0, 1, (B, 10))
+    obs[:, ::2] /= 100.0
+    obs[:, 1::2] /= 30.0
+    return obs, rng.uniform(-1, 1, (B, 1))
+
+
+def _uni_rows(rng, B, heading=np.pi):
+    x = np.stack([rng.uniform(-3, 3, B), rng.uniform(-3, 3, B), rng.uniform(-heading, heading, B)], 1)
+    return O.uni_obs(x), rng.uniform(-1, 1, (B, 2))
+
+
+def _cars_draws(env, obs, act, t, base, seed, counter):
+    """The ten N(0, 1) draws of every row, recovered from next_obs: std = 1,
+    no mean, so next_obs_k = base_k + 0.02 z_k / (100 | 30) (exact to 5e-13)."""
+    from rcbf_amd.generate_rollouts import model_step
+    B = obs.shape[0]
+    n, *_ = model_step(env, obs, act, t, std=np.ones((B, 10), np.float32), z=None, seed=seed, counter=counter)
+    return (n - base).cpu().numpy() * np.where(np.arange(10) % 2, 30.0, 100.0) / 0.02
+
+
+def test_model_step_cars_draws_equal_the_keyed_oracle_draw():
+    """Cars: three Philox calls (q = 0, 1, 2) for ten components, where the
+    unicycle tests pin one call and two components.  Every row, every
+    component, four counters, a seed above 2^32: the draws equal
+    oracle.model_step_normal to 2e-5; a seed that differs in the high word
+    alone gives other draws; the pooled sample is standard normal; and the 45
+    correlations between components are below 6 / sqrt(n) -- two calls that
+    shared a Philox block (q dropped from the counter) would repeat components
+    0-3 as 4-7 and 8-9, correlation 1."""
+    from rcbf_amd.generate_rollouts import model_step
+    rng = np.random.default_rng(8)
+    B = DRAW_B
+    env = _env("SimulatedCars")
+    obs, act = _cars_rows(rng, B)
+    t = np.round(rng.uniform(0, 5, B) / 0.02) * 0.02
+    base, *_ = model_step(env, obs, act, t, std=np.ones((B, 10), np.float32), z=np.zeros((B, 10)))
+    zs, worst = [], 0.0
+    for counter in range(4):
+        z = _cars_draws(env, obs, act, t, base, DRAW_SEED, counter)
+        want = O.model_step_normal(DRAW_SEED, np.arange(B), counter, 10)
+        diff = np.abs(z - want).max(0)
+        worst = max(worst, float(diff.max()))
+        print(f"cars draws, counter {counter}: largest |z - oracle| per component {diff}")
+        assert diff.max() <= DRAW_TOL, (counter, diff)
+        zs.append(z)
+    print(f"cars draws: largest |z - oracle| over {4 * B} rows x 10 components: {worst:.3g} (bar {DRAW_TOL})")
+    other = (8 << 32) | 11  # the low word and everything else the same
+    z2 = _cars_draws(env, obs, act, t, base, other, 0)
+    assert np.abs(z2 - O.model_step_normal(other, np.arange(B), 0, 10)).max() <= DRAW_TOL
+    assert np.mean(np.abs(z2 - zs[0])) > 1.0  # independent N(0, 1): E |a - b| = 2 / sqrt(pi) = 1.128
+    zs = np.concatenate(zs)
+    _assert_standard_normal(O.normal_moments(zs), zs.size)
+    corr = np.corrcoef(zs.T)
+    off = np.abs(corr[~np.eye(10, dtype=bool)])
+    assert off.size == 90 and off.max() < 6.0 / np.sqrt(zs.shape[0]), off.max()
+
+
+def test_model_step_unicycle_heading_draw_equals_the_keyed_oracle_draw():
+    """Component 2 of the unicycle's one Philox call, recovered as the
+    difference of the headings atan2(sin, cos) of next_obs (start headings in
+    (-3, 3): with |dt u| <= 0.02 and |dt sd z| <= 0.024 nothing wraps), and
+    components 0 and 1 under the same seed above 2^32."""
+    from rcbf_amd.generate_rollouts import model_step
+    rng = np.random.default_rng(9)
+    B = DRAW_B
+    env = _env("Unicycle")
+    obs, act = _uni_rows(rng, B, heading=3.0)
+    base, *_ = model_step(env, obs, act, z=np.zeros((B, 3)))
+    base = base.cpu().numpy()
+    worst = 0.0
+    for counter in range(4):
+        n, *_ = model_step(env, obs, act, z=None, seed=DRAW_SEED, counter=counter)
+        n = n.cpu().numpy()
+        z = np.stack([n[:, 0] - base[:, 0], n[:, 1] - base[:, 1],
+                      np.arctan2(n[:, 3], n[:, 2]) - np.arctan2(base[:, 3], base[:, 2])], 1) / (0.02 * 0.2)
+        diff = np.abs(z - O.model_step_normal(DRAW_SEED, np.arange(B), counter, 3)).max(0)
+        worst = max(worst, float(diff.max()))
+        assert diff.max() <= DRAW_TOL, (counter, diff)
+    print(f"unicycle draws: largest |z - oracle| over {4 * B} rows x 3 components: {worst:.3g} (bar {DRAW_TOL})")
+
+
+def _against_the_oracle(mode, obs, act, t, z, mean=None, std=None):
+    """One launch against oracle.model_rollout_step at the file's bars; returns
+    the oracle's outputs and the largest differences seen."""
+    from rcbf_amd.generate_rollouts import model_step
+    nobs, r, mask, nt = (v.cpu().numpy() for v in model_step(_env(mode), obs, act, t, mean=mean, std=std, z=z))
+    on, orr, om, ot = O.model_rollout_step(mode, obs, act, t, z, mean=mean, std=std)
+    d_obs, d_r = float(np.max(np.abs(nobs - on))), float(np.max(np.abs(r - orr)))
+    print(f"{mode} B = {obs.shape[0]}: next_obs {d_obs:.3g}, reward {d_r:.3g} (bar 1e-12)")
+    assert d_obs <= 1e-12 and d_r <= 1e-12
+    assert np.array_equal(mask, om) and np.array_equal(nt, ot)
+    return (on, orr, om, ot), (nobs, r, mask, nt)
+
+
+def _gp_rows(rng, B, n_s):
+    return rng.normal(0, 0.1, (B, n_s)).astype(np.float32), rng.uniform(0.01, 0.3, (B, n_s)).astype(np.float32)
+
+
+def test_model_step_unicycle_around_the_goal():
+    """Rows that end within 0.1 of the goal radius, inside and outside it: the
+    goal branch (mask 0, the bonus added twice) with the prior and with GP
+    mean / std rows."""
+    rng = np.random.default_rng(0)
+    B = 777
+    r, a = rng.uniform(0.2, 0.4, B), rng.uniform(-np.pi, np.pi, B)
+    x = np.stack([2.5 - r * np.cos(a), 2.5 - r * np.sin(a), rng.uniform(-np.pi, np.pi, B)], 1)
+    obs, act = O.uni_obs(x), rng.uniform(-1, 1, (B, 2))
+    z = rng.normal(0, 1, (B, 3))
+    for mean, std in ((None, None), _gp_rows(rng, B, 3)):
+        (on, orr, om, ot), (nobs, rew, mask, nt) = _against_the_oracle("Unicycle", obs, act, None, z, mean, std)
+        g = np.array([2.5, 2.5]) - on[:, :2]
+        d = np.linalg.norm(g, axis=1)  # the oracle's own d
+        print(f"  min |d - 0.3| = {np.abs(d - 0.3).min():.3g}, {int((d <= 0.3).sum())} of {B} rows reach the goal")
+        assert np.abs(d - 0.3).min() > 1e-9  # no row whose branch a last-bit difference in d could flip
+        goal = d <= 0.3
+        assert goal.sum() >= 100 and (~goal).sum() >= 100
+        assert np.array_equal(mask, np.where(goal, 0.0, 1.0))
+        shaped = -np.log(obs[:, -1]) - d
+        assert np.max(np.abs(rew[goal] - shaped[goal] - 2.0)) <= 1e-12  # the bonus, twice
+        assert np.max(np.abs(rew[~goal] - shaped[~goal])) <= 1e-12
+        assert np.array_equal(nt, np.full(B, 0.02))
+
+
+def test_model_step_cars_mask_at_the_time_limit():
+    """t as the replay packer stores it (k * 0.02) and as k additions of 0.02,
+    k = 295 .. 301: the two differ in their last bits, and at k = 299 on the
+    two sides of the limit -- 299 * 0.02 + 0.02 >= 6.0, the 299-fold sum + 0.02
+    is not.  Kernel and oracle agree on every row, with the prior and with GP
+    mean / std rows (which no other test gives the cars in this kernel)."""
+    rng = np.random.default_rng(1)
+    B = 777
+    obs, act = _cars_rows(rng, B)
+    k = 295 + np.arange(B) % 7
+    summed = np.zeros(302)
+    for n in range(1, 302):
+        summed[n] = summed[n - 1] + 0.02
+    as_sum = (np.arange(B) // 7) % 2 == 1
+    t = np.where(as_sum, summed[k], k * 0.02)
+    assert np.any(summed[295:302] != np.arange(295, 302) * 0.02)
+    assert 299 * 0.02 + 0.02 >= 6.0 and not summed[299] + 0.02 >= 6.0
+    z = rng.normal(0, 1, (B, 10))
+    for mean, std in ((None, None), _gp_rows(rng, B, 10)):
+        (on, orr, om, ot), _ = _against_the_oracle("SimulatedCars", obs, act, t, z, mean, std)
+        assert om[(k == 299) & ~as_sum].max() == 0.0 and om[(k == 299) & as_sum].min() == 1.0
+        assert om[k <= 298].min() == 1.0 and om[k >= 300].max() == 0.0
+        assert (om == 0.0).sum() >= 100 and (om == 1.0).sum() >= 100
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+@pytest.mark.parametrize("B", [1, 257])
+def test_model_step_small_and_ragged_batches(mode, B):
+    rng = np.random.default_rng(10 + B)
+    cars = mode == "SimulatedCars"
+    obs, act = _cars_rows(rng, B) if cars else _uni_rows(rng, B)
+    t = np.round(rng.uniform(0, 6, B) / 0.02) * 0.02
+    n_s = 10 if cars else 3
+    _against_the_oracle(mode, obs, act, t, rng.normal(0, 1, (B, n_s)))
+    _against_the_oracle(mode, obs, act, t, rng.normal(0, 1, (B, n_s)), *_gp_rows(rng, B, n_s))
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+def test_model_step_null_next_t(mode):
+    """The C ABI with next_t = NULL: rc == 0, and next_obs, reward and mask are
+    bit-equal to the call that passes it; nothing is written past them."""
+    import ctypes
+
+    from rcbf_amd import _lib
+    from rcbf_amd.params import make_params
+    rng = np.random.default_rng(12)
+    B, sent = 257, -4321.25
+    cars = mode == "SimulatedCars"
+    obs, act = _cars_rows(rng, B) if cars else _uni_rows(rng, B)
+    dev = torch.device("cuda", 0)
+    obs, act = torch.tensor(obs, device=dev), torch.tensor(act, device=dev)
+    t = torch.tensor(np.round(rng.uniform(0, 6, B) / 0.02) * 0.02, device=dev)
+    prm = make_params(_env(mode), 1.0)
+    outs = []
+    for with_t in (True, False):
+        nobs = torch.full((B + 1, obs.shape[1]), sent, dtype=torch.float64, device=dev)
+        rew, mask, nt = (torch.full((B + 1,), sent, dtype=torch.float64, device=dev) for _ in range(3))
+        rc = _lib.load().rcbf_model_step(ctypes.byref(prm), B, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(t), None, None,
+                                         None, 5, 3, _lib.ptr(nobs), _lib.ptr(rew), _lib.ptr(mask),
+                                         _lib.ptr(nt if with_t else None), _lib.stream_of(dev))
+        assert rc == 0
+        torch.cuda.synchronize()
+        assert all(v[B:].eq(sent).all() and not v[:B].eq(sent).any() for v in (nobs, rew, mask))
+        outs.append((nobs, rew, mask))
+        if with_t:
+            assert torch.equal(nt[:B], t + 0.02) and nt[B].item() == sent
+        else:
+            assert bool(nt.eq(sent).all())
+    assert all(torch.equal(a.view(torch.int64), b.view(torch.int64)) for a, b in zip(*outs))

@@ -45,6 +45,7 @@ import numpy as np
 import pytest
 import torch
 
+from _traj_grid import chunk as _chunk
 from test_gpu_traj_replay import DIMS, _Env, _synthetic
 
 pytestmark = pytest.mark.gpu
@@ -267,14 +268,6 @@ def test_keep_last_is_the_tail_of_the_unlimited_result_and_the_rest_stays_untouc
     assert _host_loop(twin, env, traj, obs0, step0, 5, 2) == n_sel
     _close(mode, full_s[:n_sel].cpu().numpy(), full_d[:n_sel].cpu().numpy(),
            twin.disturbance_history["state"][:n_sel], twin.disturbance_history["disturbance"][:n_sel])
-
-
-def _chunk(B, K):
-    """Steps per workgroup the library picks for (B, K) on this device
-    (traj_steps_per_workgroup in csrc/rcbf_model.hip)."""
-    waves, want = (B + 63) // 64, 8 * torch.cuda.get_device_properties(0).multi_processor_count
-    parts = min(1 if waves >= want else -(-want // waves), K, 65535)
-    return -(-K // parts)
 
 
 def _rows_against_the_host_loop(mode, B, P, K, every, seed):

@@ -238,3 +238,136 @@ def test_term_obs_plan_into_replay_end_to_end():
         plan.free()
     finally:
         q.close()
+
+
+# Several steps per workgroup.  The shapes above give every workgroup ONE step (waves x K is far below 8 waves
+# per CU), so the row and the count a lane carries from step to step, the barrier between two steps' records and
+# a cut or a wrap at a step inside a chunk never run there.  B = 8 256 (129 waves) at pitch 8 320, K = 40: on a
+# 256-CU device 14 chunks, 13 of 3 steps and the last of 1.  Every test asserts what it needs of the grid.
+GRID_B, GRID_P, GRID_K = 8256, 8320, 40
+
+
+def _grid_chunk():
+    from _traj_grid import chunk
+    c = chunk(GRID_B, GRID_K)
+    assert 3 <= c < GRID_K and GRID_K % c == 1, c  # first, middle and last steps; the last chunk is one step
+    return c
+
+
+def _episode_steps(traj, step0, K, auto_reset=True):
+    """e (K, B): the post-increment episode step of every transition, and done (K, B)."""
+    done = traj["done"][:K] != 0
+    c, e = step0.to(torch.int64).clone(), []
+    for j in range(K):
+        e.append(c + 1)
+        c = torch.where(done[j] & bool(auto_reset), torch.zeros_like(c), e[-1])
+    return torch.stack(e), done
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+def test_several_steps_per_workgroup_equal_batch_push(mode):
+    """Resets and the time limit land on first, middle and last steps of
+    chunks: the row carried to the next step is the reset row (not the terminal
+    row), the count carried is 0 after a reset."""
+    B, P, K, seed = GRID_B, GRID_P, GRID_K, 61
+    chunk = _grid_chunk()
+    env = _Env(mode, B)
+    traj, _, step0 = _synthetic(env, K, P, seed)  # what _case(seed=seed) packs
+    e, done = _episode_steps(traj, step0, K)
+    j = torch.arange(K, device="cuda")
+    first, last = j % chunk == 0, (j % chunk == chunk - 1) | (j == K - 1)
+    middle = ~first & ~last
+    assert int(middle.sum()) >= K // chunk
+    lim = e == env.max_episode_steps
+    for where in (first, middle, last):  # (a middle step has a later step in its chunk)
+        assert bool(done[where].any()) and bool(lim[where].any())
+    # ... and an env is done on a middle step and again on a later step of the same chunk
+    assert any(bool((done[m] & done[n]).any()) for m in torch.nonzero(middle)[:, 0].tolist()
+               for n in range(m + 1, min((m // chunk + 1) * chunk, K)))
+    for position in (0, 7):
+        _case(mode, B, K, P, K * B + 37, position, seed=seed)
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+def test_several_steps_per_workgroup_without_term_obs(mode):
+    """auto_reset=False: the count runs through done (every env reaches the
+    time limit inside the plan); auto_reset=True without term_obs: next_obs is
+    the reset row, the count restarts."""
+    B, P, K, seed = GRID_B, GRID_P, GRID_K, 62
+    chunk = _grid_chunk()
+    env = _Env(mode, B)
+    traj, _, step0 = _synthetic(env, K, P, seed)
+    e, done = _episode_steps(traj, step0, K, auto_reset=False)
+    at = torch.nonzero(e == env.max_episode_steps)[:, 0]  # the steps at which an env reaches the limit
+    assert at.numel() >= B - B // 8 and {int(v) for v in (at % chunk).unique()} == set(range(chunk))
+    assert bool(done[:-1].any())
+    _case(mode, B, K, P, K * B + 37, 7, term=False, auto_reset=False, seed=seed)
+    _case(mode, B, K, P, K * B + 37, 7, term=False, auto_reset=True, seed=seed)
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+def test_wrap_inside_a_chunk_of_several_steps(mode):
+    """The ring's end falls inside the 64 records of wave w at step j, `head`
+    of them before it: on the first, the middle and the last step of a chunk,
+    after a wave's first record (head = 1) and before its last (head = 63)."""
+    B, P, K = GRID_B, GRID_P, GRID_K
+    chunk = _grid_chunk()
+    cap, j0 = K * B + 37, 5 * chunk
+    cuts = [(j0, 77, 33), (j0 + chunk // 2, 77, 33), (j0 + chunk - 1, 77, 33), (j0 + chunk // 2, 3, 1),
+            (j0 + chunk // 2, 128, 63)]
+    for j, w, head in cuts:
+        position = cap - (j * B + 64 * w + head)
+        assert 0 < position < cap and 0 < head < 64 and 64 * w + 64 <= B
+        _case(mode, B, K, P, cap, position, seed=j + w)
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+def test_more_transitions_than_capacity_cuts_inside_a_chunk(mode):
+    """capacity = K B - skip, the first kept transition inside a step in the
+    middle of a chunk, on a chunk's first and last step, on a step's first row,
+    on the last row before the one-step last chunk and inside it, and a
+    one-slot ring; the ring starts empty and one slot before its end."""
+    B, P, K = GRID_B, GRID_P, GRID_K
+    chunk = _grid_chunk()
+    mid, last = chunk + chunk // 2, K - 1
+    assert 0 < mid % chunk < chunk - 1 and last % chunk == 0
+    skips = [mid * B + 100, mid * B, chunk * B + 64 + 7, (2 * chunk - 1) * B + 4000, last * B + 5, last * B - 1,
+             K * B - 1]
+    for skip in skips:
+        capacity = K * B - skip
+        assert 0 < capacity < K * B
+        for position in sorted({0, capacity - 1}):
+            _case(mode, B, K, P, capacity, position, seed=skip % 1000)
+
+
+@pytest.mark.parametrize("mode", ["SimulatedCars", "Unicycle"])
+def test_a_last_wave_of_32_envs_with_several_steps_per_workgroup(mode):
+    """8 256 and 65 600 are multiples of 64.  B = 8 224 at the same pitch and K
+    (129 waves, the same chunks): the last wave holds 32 envs, its block of a
+    step is 32 records; the ring wraps inside it on a chunk's middle step, and
+    a cut falls inside it."""
+    from _traj_grid import chunk as grid_chunk
+    B, P, K = GRID_B - 32, GRID_P, GRID_K
+    chunk = grid_chunk(B, K)
+    assert chunk == _grid_chunk() and B % 64 == 32
+    j, w = 4 * chunk + chunk // 2, B // 64
+    cap = K * B + 37
+    _case(mode, B, K, P, cap, cap - (j * B + 64 * w + 9), seed=71)
+    skip = j * B + 64 * w + 9
+    _case(mode, B, K, P, K * B - skip, 0, seed=72)
+
+
+def test_the_flagship_grid_ten_steps_per_workgroup_cars():
+    """B = 65 600 (1 025 waves) at pitch 65 664, K = 19: the grid training
+    runs, two chunks of 10 and 9 steps on a 256-CU device; the ring wraps
+    inside the last wave's records of step 4."""
+    from _traj_grid import chunk
+    B, P, K = 65600, 65664, 19
+    assert 8 < chunk(B, K) < K
+    cap = K * B + 37
+    position = cap - (4 * B + 64 * 1024 + 9)
+    assert 0 < position < cap and B == 64 * 1025
+    mem, twin = _case("SimulatedCars", B, K, P, cap, position, seed=63)
+    assert len(mem) == cap and mem.position == (position + K * B) % cap
+    del mem._ring, twin._ring, mem, twin  # 250 MB each
+    torch.cuda.empty_cache()
