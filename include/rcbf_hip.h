@@ -782,6 +782,67 @@ int rcbf_aql_plan_dispatches(const rcbf_aql_plan* plan);
 int rcbf_aql_plan_free(rcbf_aql_plan* plan);
 
 /* ---------------------------------------------------------------------- */
+/* Policy network forward (the actor's inference pass)                     */
+/* ---------------------------------------------------------------------- */
+/* GaussianPolicy.forward / .sample without log_prob (rcbf_sac/model.py:86-106;
+ * DeterministicPolicy.forward, model.py:135-139, is the MEAN mode), the
+ * network behind agent.select_action (sac_cbf.py:72-75), one launch, fp32:
+ *   h1 = relu(W1 obs + b1);  h2 = relu(W2 h1 + b2);  mean = Wm h2 + bm
+ *   log_std = clamp(Ws h2 + bs, -20, 2)
+ *   RCBF_POLICY_MEAN   (evaluate=True):  u = tanh(mean) * scale + bias
+ *   RCBF_POLICY_SAMPLE (evaluate=False): u = tanh(mean + exp(log_std) * z) * scale + bias
+ * obs (B, n_o) f32 -> u_rl (B, n_u) f32; 1 <= n_o <= 16, n_u in {1, 2},
+ * hidden a multiple of 32 in [32, 256] (RCBF_E_BAD_SHAPE otherwise).
+ *
+ * Summation order (fixed): every pre-activation is one fp32 chain
+ *   a = b[j];  for k = 0, 1, 2, ...:  a = fmaf(W[j][k], x[k], a)
+ * with the bias as the first value and k ascending; n_o is padded with one
+ * zero column to an even count.  The hidden layers run on the fp32 MFMA
+ * (bit for bit this chain), the heads on the VALU in the same order; tanh,
+ * exp and the affine map are evaluated per element (mean + std * z and
+ * y * scale + bias as separate roundings, as torch evaluates them).  A row's
+ * action therefore depends on that row (and, when z is null, its global index)
+ * alone: not on B, not on its place in the batch.  torch's Linear sums in
+ * blocks whose shape depends on the GEMM kernel the batch size selects, so the
+ * two agree to fp32 rounding, not bit for bit.
+ *
+ * z [SAMPLE only, nullable] (B, n_u) f32 N(0,1) draws.  Null: component c of
+ * row i is the model step's draw (rcbf_model_step with z == NULL) for row
+ * env_offset + i: Philox4x32-10 keyed by seed on the counter
+ * (row lo, row hi, counter lo, 0), Box-Muller on 24-bit uniforms, c = 0 the
+ * cosine and c = 1 the sine branch; a shard with env_offset = its first global
+ * row draws what the whole batch would.
+ *
+ * packed: one device buffer of rcbf_policy_packed_floats(n_o, n_u, hidden)
+ * floats, 16-byte aligned, every section a multiple of 4 floats.  With
+ * H = hidden, K1 = n_o + (n_o & 1), lane l = 0..63 (the MFMA A-operand lane:
+ * unit l & 31 of a 32-unit block, k parity l >> 5):
+ *   W1p   H K1    [cb < H/32][s < K1/2][l]       = W1[32 cb + (l & 31)][2 s + (l >> 5)]  (0 for k >= n_o)
+ *   b1    H
+ *   W2p   H H     [cb < H/32][s4 < H/8][l][j<4]  = W2[32 cb + (l & 31)][2 (4 s4 + j) + (l >> 5)]
+ *   b2    H
+ *   Wm    n_u H   row-major
+ *   bm    4       (n_u used)
+ *   Ws    n_u H   row-major (zeros for a module without a log-std head)
+ *   bs    4
+ *   action_scale 4, action_bias 4  (n_u used)
+ * in this order: H (K1 + H + 2 + 2 n_u) + 16 floats (-1 for a bad shape).
+ * rcbf_amd.policy.DevicePolicy packs a torch module into it.
+ *
+ * Stateless and capturable; rows past B are neither read nor written.  B = 0
+ * returns 0 without a launch.  Errors before any launch: RCBF_E_BAD_SHAPE (a
+ * shape above, B < 0 or B > 2^31 - 1 (the grid is a workgroup per 32 or 64
+ * rows), env_offset < 0, packed not 16-byte or obs / u_rl / z not 4-byte
+ * aligned), RCBF_E_BAD_MODE (unknown mode), RCBF_E_NULL (packed, obs or u_rl
+ * null). */
+#define RCBF_POLICY_MEAN 0
+#define RCBF_POLICY_SAMPLE 1
+int64_t rcbf_policy_packed_floats(int32_t n_o, int32_t n_u, int32_t hidden);
+int rcbf_policy_act(const float* packed, int32_t n_o, int32_t n_u, int32_t hidden, int64_t B,
+                    const float* obs, float* u_rl, int32_t mode, const float* z,
+                    uint64_t seed, uint64_t counter, int64_t env_offset, hipStream_t stream);
+
+/* ---------------------------------------------------------------------- */
 const char* rcbf_version(void);
 int32_t rcbf_abi_version(void);
 /* sizeof(rcbf_params) as compiled, for binding checks (no GPU needed). */

@@ -2271,6 +2271,17 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
     }
 }
 
+// One Box-Muller pair from two Philox words: 24-bit uniforms, f1 in (0, 1] and f2 in [0, 1) revolutions, with
+// the hardware fp32 log2 / cos / sin (v_cos_f32 and v_sin_f32 take revolutions).  |z| <= sqrt(48 ln 2) = 5.77.
+// The model step's and the policy's draws (oracle.model_step_normal); normal_draw below is its cosine branch.
+__device__ __forceinline__ void box_muller_pair(uint32_t w1, uint32_t w2, float& zc, float& zs) {
+    const float f1 = ((float)(w1 >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    const float f2 = (float)(w2 >> 8) * (1.0f / 16777216.0f);
+    const float r = __builtin_sqrtf(-2.0f * __builtin_amdgcn_logf(f1) * 0.69314718f);
+    zc = r * __builtin_amdgcn_cosf(f2);
+    zs = r * __builtin_amdgcn_sinf(f2);
+}
+
 // Reset draw: Box-Muller on 24-bit uniforms with the hardware fp32
 // log2/cos -- ~10 instructions instead of ~170 for an fp64 libm path; the
 // reset branch is on the critical path of whichever wave holds a resetting

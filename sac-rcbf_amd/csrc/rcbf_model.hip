@@ -178,12 +178,11 @@ __global__ void __launch_bounds__(kBlock) k_model_step(rcbf_params prm, int64_t 
             philox4x32_10(cc, (uint32_t)seed, (uint32_t)(seed >> 32));
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const float f1 = ((float)(cc[2 * h] >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-                const float f2 = (float)(cc[2 * h + 1] >> 8) * (1.0f / 16777216.0f);      // [0, 1) revolutions
-                const float r = __builtin_sqrtf(-2.0f * __builtin_amdgcn_logf(f1) * 0.69314718f);
+                float zc, zs;
+                box_muller_pair(cc[2 * h], cc[2 * h + 1], zc, zs);
                 const int k = 4 * q + 2 * h;
-                if (k < NS) zz[k] = (double)(r * __builtin_amdgcn_cosf(f2));
-                if (k + 1 < NS) zz[k + 1] = (double)(r * __builtin_amdgcn_sinf(f2));
+                if (k < NS) zz[k] = (double)zc;
+                if (k + 1 < NS) zz[k + 1] = (double)zs;
             }
         }
     }

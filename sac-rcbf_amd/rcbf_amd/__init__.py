@@ -11,8 +11,12 @@ safety-layer QP, as hand-written HIP kernels for gfx950 behind a C-ABI
   rcbf_amd.envs.Batched*Env (+ safe_step / rollout: the fused kernels)
   rcbf_amd.build_env.build_env          <- build_env.py
   rcbf_amd.EpisodeStats (episode_stats) <- main.py:98-101,140-144, the loop's episode bookkeeping
+  rcbf_amd.DevicePolicy (policy)        <- rcbf_sac/model.py:86-106, the actor's inference forward (one launch)
+  rcbf_amd.evaluate_policy (evaluator)  <- main.py:146-177, the evaluation loop on B envs
 """
 from . import _lib  # noqa: F401
 from .episode_stats import EpisodeStats  # noqa: F401
+from .evaluator import evaluate_policy  # noqa: F401
+from .policy import DevicePolicy  # noqa: F401
 
 __version__ = "0.1.0"

@@ -21,6 +21,8 @@ FORM_CASCADE = 1
 SOLVER_ACTIVE_SET = 0
 SOLVER_PDIPM = 1
 SOLVER_GI = 2
+POLICY_MEAN = 0
+POLICY_SAMPLE = 1
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NONFINITE = 0, 1, 2, 3
 MAX_HAZARDS = 8
 ABI_VERSION = 13
@@ -144,6 +146,9 @@ SIGNATURES = {
     "rcbf_traj_episode_stats_f64": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _I32,
                                     _I64, _P],
     "rcbf_traj_episode_stats_scratch_bytes": [_I64, _I32],
+    # the policy forward: packed, n_o, n_u, hidden, B, obs, u_rl, mode, z, seed, counter, env_offset, stream
+    "rcbf_policy_act": [_P, _I32, _I32, _I32, _I64, _P, _P, _I32, _P, _U64, _U64, _I64, _P],
+    "rcbf_policy_packed_floats": [_I32, _I32, _I32],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],
@@ -179,6 +184,7 @@ def load():
     lib.rcbf_gp_workspace_floats.restype = ctypes.c_int64
     lib.rcbf_traj_pack_gp_scratch_bytes.restype = ctypes.c_int64
     lib.rcbf_traj_episode_stats_scratch_bytes.restype = ctypes.c_int64
+    lib.rcbf_policy_packed_floats.restype = ctypes.c_int64
     if lib.rcbf_abi_version() != ABI_VERSION or lib.rcbf_params_size() != ctypes.sizeof(RcbfParams):
         raise RuntimeError("librcbf_hip.so ABI mismatch (rebuild with `python __graft_entry__.py build`)")
     _bind_fast(lib)
