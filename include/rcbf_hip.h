@@ -728,7 +728,50 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
  *     span_out, RCBF_AQL_PROFILE, RCBF_AQL_STUDY_*, RCBF_AQL_PER_STEP, a u_RL
  *     buffer that overlaps a written buffer (term_obs's whole (K, P, n_o)
  *     extent included), a queue opened without librcbf_steps_term.co.
- *     RCBF_AQL_PROFILE_ENDS works. */
+ *     RCBF_AQL_PROFILE_ENDS works.
+ *
+ * rcbf_aql_closed_loop_plan: K steps whose actions the POLICY computes between
+ * them (rcbf_policy_act below, from the observation the step before left):
+ * the reference's data-collection and evaluation loops (main.py:86-130,
+ * main.py:146-177, rcbf_sac/evaluator.py:20-54: agent.select_action ->
+ * env.step) as one doorbell per K steps of B envs.  The arguments of
+ * rcbf_aql_safe_step_term_plan with the action sequence replaced by ONE
+ * action buffer u_rl_buf (B, n_u) fp32, then obs_in, what step 0's policy
+ * reads (the env's observation buffer), then the policy's arguments: packed,
+ * n_o, n_u, hidden, mode, seed as rcbf_policy_act takes them, counter_word
+ * and policy_env_offset (rcbf_policy_act's env_offset).
+ *   - 2K packets, barrier bit on each, the per-step form's fences.  Packet
+ *     2j is the policy (rcbf::k_policy_step, from librcbf_policy.co, 256
+ *     threads per 32 or 64 rows by rcbf_policy_act's rule, its dynamic LDS
+ *     size carried by the packet): it reads the observation step j - 1 left
+ *     -- obs_in for j = 0, row j - 1 of the obs array when RCBF_TRAJ_OBS is
+ *     recorded, obs_out otherwise -- and writes u_rl_buf.  Packet 2j + 1 is
+ *     step j reading u_rl_buf: k_safe_step with step j's row pointers, or,
+ *     with RCBF_TRAJ_TERM_OBS, a one-step dispatch of k_safe_steps_term at
+ *     row j (exact active set only, RCBF_E_BAD_MODE otherwise).  Every output
+ *     is that of K alternating rcbf_policy_act / rcbf_safe_step launches,
+ *     recorded as rcbf_aql_safe_step_traj_plan / _term_plan record them;
+ *     u_rl_buf holds the last step's policy action.  A plan whose obs is
+ *     recorded does not write obs_in: copy row K - 1 there before the next
+ *     run.
+ *   - RCBF_POLICY_SAMPLE draws in the kernel only (no z): packet 2j draws
+ *     with the counter *counter_word + j, read when the packet runs, so the
+ *     caller sets the word (device-visible memory, 8-byte aligned) before
+ *     every run and the same plan draws fresh noise; a NULL counter_word
+ *     counts as 0.  RCBF_POLICY_MEAN reads neither.
+ *   - RCBF_AQL_PROFILE_ENDS works (row 0: the first policy packet, row
+ *     K - 1: the last step; K = 1: the policy's start and the step's end).
+ *     RCBF_AQL_PROFILE, span_out and RCBF_AQL_STUDY_*: RCBF_E_BAD_MODE.
+ *   - Checked before anything is allocated: the null, shape and alignment
+ *     rules of rcbf_aql_safe_step_term_plan and of rcbf_policy_act; n_o and
+ *     n_u equal the env mode's (RCBF_E_BAD_SHAPE); u_rl_buf overlaps nothing
+ *     else that a packet reads or writes, the whole extent of every recorded
+ *     array included (RCBF_E_BAD_SHAPE).
+ *   - A queue opened without librcbf_policy.co (or whose four kernels do not
+ *     take the RCBF_AQL_POLICY_STEP_KERNARG_BYTES block): RCBF_E_BAD_MODE;
+ *     every other call on that queue is unaffected.
+ * rcbf_aql_plan_dispatches returns 2K; rcbf_aql_run, rcbf_aql_plan_times and
+ * rcbf_aql_plan_free work on these plans unchanged. */
 #define RCBF_TRAJ_OBS 1
 #define RCBF_TRAJ_U 2
 #define RCBF_TRAJ_REWARD 4
@@ -751,6 +794,7 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
 #define RCBF_AQL_SAFE_STEPS_KERNARG_BYTES 408 /* sizeof the k_safe_steps (fused form) argument block */
 #define RCBF_AQL_SAFE_STEPS_TRAJ_KERNARG_BYTES 424 /* ... of k_safe_steps_traj: + traj_mask (408), traj_pitch (416) */
 #define RCBF_AQL_SAFE_STEPS_TERM_KERNARG_BYTES 432 /* ... of k_safe_steps_term: + term_obs (424) */
+#define RCBF_AQL_POLICY_STEP_KERNARG_BYTES 80 /* sizeof the k_policy_step argument block (closed-loop plans) */
 typedef struct rcbf_aql rcbf_aql;
 typedef struct rcbf_aql_plan rcbf_aql_plan;
 int rcbf_aql_open(int32_t device, const char* code_object, int32_t flags, rcbf_aql** out);
@@ -776,6 +820,15 @@ int rcbf_aql_safe_step_term_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B,
                                  int32_t* status_out, int32_t* fail_flag, int32_t auto_reset, uint64_t seed,
                                  int64_t env_offset, uint64_t* span_out, int32_t flags, int32_t traj_mask,
                                  int64_t traj_pitch, float* term_obs, rcbf_aql_plan** out);
+int rcbf_aql_closed_loop_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                              int32_t* step, uint32_t* episode, float* u_rl_buf, const float* mu, const float* sigma,
+                              int32_t prior_cols, float* obs_out, float* u_out, float* reward, float* cost,
+                              uint8_t* done, uint8_t* goal_met, int32_t* status_out, int32_t* fail_flag,
+                              int32_t auto_reset, uint64_t seed, int64_t env_offset, uint64_t* span_out,
+                              int32_t flags, int32_t traj_mask, int64_t traj_pitch, float* term_obs,
+                              const float* obs_in, const float* packed, int32_t n_o, int32_t n_u, int32_t hidden,
+                              int32_t mode, uint64_t policy_seed, const uint64_t* counter_word,
+                              int64_t policy_env_offset, rcbf_aql_plan** out);
 int rcbf_aql_run(rcbf_aql_plan* plan, uint64_t timeout_us);
 int rcbf_aql_plan_times(const rcbf_aql_plan* plan, uint64_t* start_end_ns);
 int rcbf_aql_plan_dispatches(const rcbf_aql_plan* plan);

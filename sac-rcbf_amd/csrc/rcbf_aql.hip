@@ -39,6 +39,13 @@
 // solvers, span / per-dispatch-profiled / study plans, RCBF_AQL_PER_STEP and
 // action buffers that alias an output.
 //
+// The closed-loop form (rcbf_aql_closed_loop_plan).  When the policy acts between the steps, step j's action
+// is not known before the run: it is what the actor computes from the observation step j - 1 left.  Such a
+// plan is 2K packets, a policy packet (rcbf::k_policy_step, from librcbf_policy.co) before every step packet,
+// each with the barrier bit and the per-step form's fences: the policy writes one (B, n_u) action buffer, the
+// step reads it and leaves the observation the next policy packet reads.  Per-step by nature, it never takes
+// the fused form; with RCBF_TRAJ_TERM_OBS its step packets are one-step dispatches of k_safe_steps_term.
+//
 // Reference interface this serves: env.step() of the batched env inside the
 // SAC loop (main.py:93-95, sac_cbf.py:218-238) -- a synchronous call, like a
 // gym step: rcbf_aql_run returns when the K steps have completed.
@@ -58,6 +65,7 @@
 #include <vector>
 
 #include "rcbf_hip.h"
+#include "rcbf_policy_step.hpp"  // PolicyStepArgs, the policy packet of a closed-loop plan
 #include "rcbf_safe_step.hpp"  // SafeStepsArgs (the templates in it are not instantiated here)
 
 namespace {
@@ -141,13 +149,17 @@ struct rcbf_aql {
     hsa_executable_t exe_term{};
     bool have_reader = false, have_reader_traj = false, have_exe = false, have_exe_traj = false, hsa_up = false;
     bool have_reader_term = false, have_exe_term = false;
-    std::vector<char> code, code_traj, code_term;
+    hsa_code_object_reader_t reader_policy{};  // librcbf_policy.co (the k_policy_step kernels), if there
+    hsa_executable_t exe_policy{};
+    bool have_reader_policy = false, have_exe_policy = false;
+    std::vector<char> code, code_traj, code_term, code_policy;
     std::vector<KernelInfo> kernels;
     std::atomic<int> queue_error{0};
     int profiling = 0;
     bool fused = false;  // the code object has the k_safe_steps kernels (the fused plan form)
     bool traj = false;   // ... and the k_safe_steps_traj kernels (the fused form of a trajectory plan)
     bool term = false;   // ... and the k_safe_steps_term kernels (trajectory plans with RCBF_TRAJ_TERM_OBS)
+    bool policy = false;  // the four k_policy_step kernels were found, each taking PolicyStepArgs (closed-loop plans)
 };
 
 struct rcbf_aql_plan {
@@ -245,11 +257,36 @@ std::string safe_steps_term_prefix(int mode, int k, int bs) {
     return buf;
 }
 
+// ... and of rcbf::k_policy_step<SAMPLE, NRB> (PolicyStepArgs)
+std::string policy_step_prefix(bool sample, int nrb) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "_ZN4rcbf13k_policy_stepILb%dELi%dEEEv", sample ? 1 : 0, nrb);
+    return buf;
+}
+
+bool read_optional_code_object(const std::string& tpath, std::vector<char>& code);
+
 // The optional code object NAME<suffix>.co beside NAME.co, read whole into `code` (left empty when the file is
 // not there).  false: there, but unreadable -- an error, not a quiet fall back.
 bool read_side_code_object(const std::string& path, const char* suffix, std::vector<char>& code) {
     if (path.size() <= 3 || path.compare(path.size() - 3, 3, ".co") != 0) return true;
-    const std::string tpath = path.substr(0, path.size() - 3) + suffix + ".co";
+    return read_optional_code_object(path.substr(0, path.size() - 3) + suffix + ".co", code);
+}
+
+// The policy kernels' code object beside NAME.co: DIR/librcbf_policy.co for DIR/librcbf_steps.co (the build's
+// names), NAME_policy.co for any other name.
+std::string policy_code_object_path(const std::string& path) {
+    static const char kSteps[] = "librcbf_steps.co";
+    const size_t n = sizeof kSteps - 1;
+    if (path.size() >= n && path.compare(path.size() - n, n, kSteps) == 0 &&
+        (path.size() == n || path[path.size() - n - 1] == '/'))
+        return path.substr(0, path.size() - n) + "librcbf_policy.co";
+    if (path.size() <= 3 || path.compare(path.size() - 3, 3, ".co") != 0) return std::string();
+    return path.substr(0, path.size() - 3) + "_policy.co";
+}
+
+bool read_optional_code_object(const std::string& tpath, std::vector<char>& code) {
+    if (tpath.empty()) return true;
     FILE* tf = fopen(tpath.c_str(), "rb");
     if (!tf) return true;
     fseek(tf, 0, SEEK_END);
@@ -271,6 +308,59 @@ bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
 }
+
+// What the argument block of every step kernel (SafeStepArgs, SafeStepsArgs) takes from the plan's arguments; the
+// action source and the form's own fields are the caller's.
+struct StepIo {
+    const rcbf_params* prm;
+    int64_t B;
+    double* x;
+    double* aux;
+    int32_t* step;
+    uint32_t* episode;
+    const float* mu;
+    const float* sigma;
+    int32_t prior_cols;
+    float* obs_out;
+    float* u_out;
+    float* reward;
+    float* cost;
+    uint8_t* done;
+    uint8_t* goal_met;
+    int32_t* status_out;
+    int32_t* fail_flag;
+    int32_t auto_reset;
+    uint64_t seed;
+    int64_t env_offset;
+    // bytes of one row of each output's (K, P, w) array; 0: not recorded (written in place)
+    int64_t row_obs, row_u, row_rew, row_cost, row_done, row_goal, row_stat;
+
+    // a zeroed block with the shared fields set, each recorded output at row r0 of its array
+    template <typename Args>
+    void fill(Args& a, int64_t r0) const {
+        std::memset(&a, 0, sizeof a);
+        a.B = B;
+        a.x = x;
+        a.aux = aux;
+        a.step = step;
+        a.episode = episode;
+        a.mu = mu;
+        a.sigma = sigma;
+        a.obs_out = rows_on(obs_out, r0, row_obs);
+        a.u_out = rows_on(u_out, r0, row_u);
+        a.reward = rows_on(reward, r0, row_rew);
+        a.cost = rows_on(cost, r0, row_cost);
+        a.done = rows_on(done, r0, row_done);
+        a.goal_met = rows_on(goal_met, r0, row_goal);
+        a.status_out = rows_on(status_out, r0, row_stat);
+        a.fail_flag = fail_flag;
+        a.auto_reset = auto_reset;
+        a.seed = seed;
+        a.off = env_offset;
+        a.prm = *prm;
+        a.prior_cols = prior_cols ? 1 : 0;
+    }
+};
 
 const KernelInfo* find_kernel(const rcbf_aql* q, const std::string& prefix) {
     const KernelInfo* hit = nullptr;
@@ -302,6 +392,8 @@ void destroy(rcbf_aql* q) {
     if (q->have_exe) hsa_executable_destroy(q->exe);
     if (q->have_exe_traj) hsa_executable_destroy(q->exe_traj);
     if (q->have_exe_term) hsa_executable_destroy(q->exe_term);
+    if (q->have_exe_policy) hsa_executable_destroy(q->exe_policy);
+    if (q->have_reader_policy) hsa_code_object_reader_destroy(q->reader_policy);
     if (q->have_reader) hsa_code_object_reader_destroy(q->reader);
     if (q->have_reader_traj) hsa_code_object_reader_destroy(q->reader_traj);
     if (q->have_reader_term) hsa_code_object_reader_destroy(q->reader_term);
@@ -352,6 +444,11 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     // ... and NAME_term.co, the kernels of the plans that keep the terminal observation: without it those
     // plans are refused (they have no per-step form) and everything else works as before
     if (!read_side_code_object(path, "_term", q->code_term)) {
+        delete q;
+        return RCBF_E_BAD_SHAPE;
+    }
+    // ... and the policy kernels of the closed-loop plans (librcbf_policy.co): without it those plans are refused
+    if (!read_optional_code_object(policy_code_object_path(path), q->code_policy)) {
         delete q;
         return RCBF_E_BAD_SHAPE;
     }
@@ -412,6 +509,20 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
         if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_term, nullptr));
         if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_term, q->agent, collect_kernel, q));
     }
+    if (!rc && !q->code_policy.empty()) {
+        rc = hsa_rc(hsa_code_object_reader_create_from_memory(q->code_policy.data(), q->code_policy.size(),
+                                                              &q->reader_policy));
+        if (!rc) q->have_reader_policy = true;
+        if (!rc)
+            rc = hsa_rc(hsa_executable_create_alt(HSA_PROFILE_FULL, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr,
+                                                  &q->exe_policy));
+        if (!rc) q->have_exe_policy = true;
+        if (!rc)
+            rc = hsa_rc(
+                hsa_executable_load_agent_code_object(q->exe_policy, q->agent, q->reader_policy, nullptr, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_policy, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_policy, q->agent, collect_kernel, q));
+    }
     // every k_safe_step instantiation in the code object must take exactly the
     // argument block SafeStepArgs describes
     // ... and every k_safe_steps instantiation SafeStepsArgs; a code object without them still opens, and
@@ -436,6 +547,15 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     q->fused = n_fused > 0;
     q->traj = n_traj > 0;
     q->term = n_term > 0;
+    // the closed-loop plans' policy kernels, {mean, sample} x {32-row, 64-row tiles}: all four, each taking
+    // PolicyStepArgs and no scratch, or no closed-loop plan is built on this queue (nothing else is affected)
+    int n_policy = 0;
+    for (int s = 0; s < 2; ++s)
+        for (int nrb = 1; nrb <= 2; ++nrb) {
+            const KernelInfo* kp = find_kernel(q, policy_step_prefix(s != 0, nrb));
+            if (kp && kp->kernarg_bytes == sizeof(PolicyStepArgs) && kp->private_bytes == 0) ++n_policy;
+        }
+    q->policy = n_policy == 4;
     if (!rc)
         rc = hsa_rc(hsa_queue_create(q->agent, kQueueSize, HSA_QUEUE_TYPE_SINGLE, queue_error_cb, q, UINT32_MAX,
                                      UINT32_MAX, &q->queue));
@@ -526,6 +646,10 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
     const int64_t row_goal = traj_mask & RCBF_TRAJ_GOAL_MET ? P : 0;
     const int64_t row_stat = traj_mask & RCBF_TRAJ_STATUS ? P * 4 : 0;
     const int64_t row_term = term ? P * (int64_t)no * 4 : 0;
+    const StepIo io{prm,     B,          x,         aux,        step,     episode,    mu,
+                    sigma,   prior_cols, obs_out,   u_out,      reward,   cost,       done,
+                    goal_met, status_out, fail_flag, auto_reset, seed,     env_offset, row_obs,
+                    row_u,   row_rew,    row_cost,  row_done,   row_goal, row_stat};
     const KernelInfo* kf = nullptr;
     // a plan that keeps the terminal observation is fused at any K (k_safe_steps_term with steps = 1 included)
     if (q->fused && (K > 1 || term) && solver == RCBF_SOLVER_ACTIVE_SET && !span_out && !(flags & kPerStepFlags))
@@ -587,27 +711,8 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
             ea.term_obs = rows_on(term_obs, r0, row_term);
             ta.traj_mask = traj_mask;
             ta.traj_pitch = traj_pitch;
-            a.B = B;
-            a.x = x;
-            a.aux = aux;
-            a.step = step;
+            io.fill(a, r0);
             a.u_tab = reinterpret_cast<const float* const*>(static_cast<unsigned char*>(p->kernargs) + table_off);
-            a.episode = episode;
-            a.mu = mu;
-            a.sigma = sigma;
-            a.obs_out = rows_on(obs_out, r0, row_obs);
-            a.u_out = rows_on(u_out, r0, row_u);
-            a.reward = rows_on(reward, r0, row_rew);
-            a.cost = rows_on(cost, r0, row_cost);
-            a.done = rows_on(done, r0, row_done);
-            a.goal_met = rows_on(goal_met, r0, row_goal);
-            a.status_out = rows_on(status_out, r0, row_stat);
-            a.fail_flag = fail_flag;
-            a.auto_reset = auto_reset;
-            a.seed = seed;
-            a.off = env_offset;
-            a.prm = *prm;
-            a.prior_cols = prior_cols ? 1 : 0;
             a.n_u = n_u_rl;
             // chunk j: steps j kFusedChunk ... of the plan; its first step reads u_rl_seq[that index % n_u_rl]
             a.steps = std::min<int32_t>(kFusedChunk, K - j * kFusedChunk);
@@ -618,28 +723,8 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
             continue;
         }
         SafeStepArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.B = B;
-        a.x = x;
-        a.aux = aux;
-        a.step = step;
+        io.fill(a, r0);
         a.u_rl = u_rl_seq[j % n_u_rl];
-        a.episode = episode;
-        a.mu = mu;
-        a.sigma = sigma;
-        a.obs_out = rows_on(obs_out, r0, row_obs);
-        a.u_out = rows_on(u_out, r0, row_u);
-        a.reward = rows_on(reward, r0, row_rew);
-        a.cost = rows_on(cost, r0, row_cost);
-        a.done = rows_on(done, r0, row_done);
-        a.goal_met = rows_on(goal_met, r0, row_goal);
-        a.status_out = rows_on(status_out, r0, row_stat);
-        a.fail_flag = fail_flag;
-        a.auto_reset = auto_reset;
-        a.seed = seed;
-        a.off = env_offset;
-        a.prm = *prm;
-        a.prior_cols = prior_cols ? 1 : 0;
         // step j's stamps: its own block of 4 ceil(B / 64) words
         a.stamp_buf = span_out ? reinterpret_cast<unsigned long long*>(span_out) + (size_t)j * 4 * ((B + 63) / 64)
                                : nullptr;
@@ -731,6 +816,226 @@ int rcbf_aql_safe_step_term_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B,
                                 env_offset, span_out, flags, traj_mask, traj_pitch, term_obs, out);
 }
 
+int rcbf_aql_closed_loop_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, int32_t K, double* x, double* aux,
+                              int32_t* step, uint32_t* episode, float* u_rl_buf, const float* mu, const float* sigma,
+                              int32_t prior_cols, float* obs_out, float* u_out, float* reward, float* cost,
+                              uint8_t* done, uint8_t* goal_met, int32_t* status_out, int32_t* fail_flag,
+                              int32_t auto_reset, uint64_t seed, int64_t env_offset, uint64_t* span_out,
+                              int32_t flags, int32_t traj_mask, int64_t traj_pitch, float* term_obs,
+                              const float* obs_in, const float* packed, int32_t n_o, int32_t n_u, int32_t hidden,
+                              int32_t mode, uint64_t policy_seed, const uint64_t* counter_word,
+                              int64_t policy_env_offset, rcbf_aql_plan** out) {
+    if (!q || !out) return RCBF_E_NULL;
+    *out = nullptr;
+    if (int e = check_prm(prm)) return e;
+    // 2 K packets, counted in an int32
+    if (B <= 0 || K <= 0 || B > INT32_MAX || K > INT32_MAX / 2) return RCBF_E_BAD_SHAPE;
+    if (!x || !aux || !step || !obs_out || !u_out || !reward || !cost || !done) return RCBF_E_NULL;
+    if (!u_rl_buf || !obs_in || !packed) return RCBF_E_NULL;
+    if ((((uintptr_t)obs_out) & 7) || (((uintptr_t)x) & 15)) return RCBF_E_BAD_SHAPE;
+    if (prior_cols && prm->mode == RCBF_MODE_SIMULATED_CARS && mu) return RCBF_E_BAD_SHAPE;
+    // per-dispatch timestamps, stamps and the study fences belong to the plans of steps alone
+    constexpr int32_t kRefused =
+        RCBF_AQL_PROFILE | RCBF_AQL_STUDY_MID_NOFENCE | RCBF_AQL_STUDY_MID_NOACQ | RCBF_AQL_STUDY_MID_NOREL;
+    if (span_out || (flags & kRefused)) return RCBF_E_BAD_MODE;
+    // the trajectory contract, as build_safe_step_plan checks it
+    const bool term = (traj_mask & RCBF_TRAJ_TERM_OBS) != 0;
+    if (term != (term_obs != nullptr)) return RCBF_E_BAD_MODE;
+    if (traj_mask & ~(kTrajAll | RCBF_TRAJ_TERM_OBS)) return RCBF_E_BAD_MODE;
+    if (!goal_met) traj_mask &= ~RCBF_TRAJ_GOAL_MET;
+    if (!status_out) traj_mask &= ~RCBF_TRAJ_STATUS;
+    if (!traj_mask) traj_pitch = 0;
+    if (traj_mask && (traj_pitch < B || traj_pitch % 4 != 0)) return RCBF_E_BAD_SHAPE;
+    if ((traj_mask & RCBF_TRAJ_OBS) && (((uintptr_t)obs_out) & 15)) return RCBF_E_BAD_SHAPE;
+    if (term && (((uintptr_t)term_obs) & 15)) return RCBF_E_BAD_SHAPE;
+    // the policy's contract, as rcbf_policy_act checks it
+    if (!policy_shape_ok(n_o, n_u, hidden) || policy_env_offset < 0) return RCBF_E_BAD_SHAPE;
+    if (mode != RCBF_POLICY_MEAN && mode != RCBF_POLICY_SAMPLE) return RCBF_E_BAD_MODE;
+    if ((((uintptr_t)packed) & 15) || (((uintptr_t)obs_in) & 3) || (((uintptr_t)u_rl_buf) & 3) ||
+        (((uintptr_t)counter_word) & 7))
+        return RCBF_E_BAD_SHAPE;
+    const bool cars = prm->mode == RCBF_MODE_SIMULATED_CARS;
+    const size_t ns = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NS : Dims<RCBF_MODE_UNICYCLE, 1>::NS;
+    const size_t no = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NO : Dims<RCBF_MODE_UNICYCLE, 1>::NO;
+    const size_t nu = cars ? Dims<RCBF_MODE_SIMULATED_CARS, 1>::NU : Dims<RCBF_MODE_UNICYCLE, 1>::NU;
+    // the policy reads the env's observation rows and writes the env's action rows
+    if ((size_t)n_o != no || (size_t)n_u != nu) return RCBF_E_BAD_SHAPE;
+    const bool ends = (flags & RCBF_AQL_PROFILE_ENDS) != 0;
+    if (ends && !q->profiling) return RCBF_E_BAD_MODE;
+    if (!q->policy) return RCBF_E_BAD_MODE;
+    // bytes of one row of each output's (K, P, w) array; 0: not recorded (written in place)
+    const int64_t P = traj_pitch;
+    const int64_t row_obs = traj_mask & RCBF_TRAJ_OBS ? P * (int64_t)no * 4 : 0;
+    const int64_t row_u = traj_mask & RCBF_TRAJ_U ? P * (int64_t)nu * 4 : 0;
+    const int64_t row_rew = traj_mask & RCBF_TRAJ_REWARD ? P * 4 : 0;
+    const int64_t row_cost = traj_mask & RCBF_TRAJ_COST ? P * 4 : 0;
+    const int64_t row_done = traj_mask & RCBF_TRAJ_DONE ? P : 0;
+    const int64_t row_goal = traj_mask & RCBF_TRAJ_GOAL_MET ? P : 0;
+    const int64_t row_stat = traj_mask & RCBF_TRAJ_STATUS ? P * 4 : 0;
+    const int64_t row_term = term ? P * (int64_t)no * 4 : 0;
+    const StepIo io{prm,     B,          x,         aux,        step,     episode,    mu,
+                    sigma,   prior_cols, obs_out,   u_out,      reward,   cost,       done,
+                    goal_met, status_out, fail_flag, auto_reset, seed,     env_offset, row_obs,
+                    row_u,   row_rew,    row_cost,  row_done,   row_goal, row_stat};
+    {
+        // the action buffer is written by every policy packet and read by every step packet: it overlaps nothing
+        // else that either of them reads or writes
+        const size_t n = (size_t)B;
+        auto ext = [K](int64_t row, size_t in_place) { return row ? (size_t)K * (size_t)row : in_place; };
+        const int64_t H = hidden, K1 = n_o + (n_o & 1);
+        const size_t packed_bytes = (size_t)(H * (K1 + H + 2 + 2 * n_u) + 16) * 4;  // rcbf_policy_packed_floats
+        const size_t prior_bytes = (prior_cols ? 3 : ns) * n * 4;
+        const struct {
+            const void* p;
+            size_t bytes;
+        } others[] = {{x, ns * n * 8},
+                      {aux, n * 8},
+                      {step, n * 4},
+                      {episode, n * 4},
+                      {obs_out, ext(row_obs, no * n * 4)},
+                      {u_out, ext(row_u, nu * n * 4)},
+                      {reward, ext(row_rew, n * 4)},
+                      {cost, ext(row_cost, n * 4)},
+                      {done, ext(row_done, n)},
+                      {goal_met, ext(row_goal, n)},
+                      {status_out, ext(row_stat, n * 4)},
+                      {term_obs, ext(row_term, 0)},
+                      {fail_flag, 4},
+                      {mu, prior_bytes},
+                      {sigma, prior_bytes},
+                      {obs_in, no * n * 4},
+                      {packed, packed_bytes},
+                      {counter_word, 8}};
+        for (const auto& w : others)
+            if (overlaps(u_rl_buf, nu * n * 4, w.p, w.bytes)) return RCBF_E_BAD_SHAPE;
+    }
+    DeviceGuard guard(q->device);
+    const int solver = prm->solver;
+    const int k = cars ? 1 : prm->num_hazards;
+    const int bs = solver == RCBF_SOLVER_ACTIVE_SET ? block_for_envs(B) : 256;
+    // the step packet: k_safe_step with step j's row pointers, or, to keep the terminal observation, a one-step
+    // dispatch of k_safe_steps_term (exact active set only) at row offset j
+    const KernelInfo* ks = nullptr;
+    if (term) {
+        if (solver != RCBF_SOLVER_ACTIVE_SET || !q->term) return RCBF_E_BAD_MODE;
+        ks = find_kernel(q, safe_steps_term_prefix(prm->mode, k, bs));
+        if (!ks || ks->kernarg_bytes != sizeof(SafeStepsTermArgs)) return RCBF_E_BAD_MODE;
+    } else {
+        ks = find_kernel(q, safe_step_prefix(solver, prm->mode, k, bs, false));
+        if (!ks || ks->kernarg_bytes != sizeof(SafeStepArgs)) return RCBF_E_BAD_MODE;
+    }
+    // the policy packet: the tile rule of rcbf_policy_act; the packet itself carries the dynamic LDS size (nothing
+    // like hipFuncSetAttribute applies to a raw dispatch): above 64 KiB from H = 256, inside gfx950's 160 KiB
+    const int nrb = B <= 32 * num_cus() ? 1 : 2;
+    const KernelInfo* kp = find_kernel(q, policy_step_prefix(mode == RCBF_POLICY_SAMPLE, nrb));
+    if (!kp || kp->kernarg_bytes != sizeof(PolicyStepArgs)) return RCBF_E_BAD_MODE;
+    const size_t policy_lds = (size_t)kp->group_bytes + policy_lds_bytes(hidden, nrb);
+    if (policy_lds > 160 * 1024) return RCBF_E_BAD_SHAPE;
+    const uint64_t step_groups = (uint64_t)grid_for_envs(B, bs);
+    const uint64_t policy_groups = (uint64_t)((B + 32 * nrb - 1) / (32 * nrb));
+    if (policy_groups * 256u > UINT32_MAX) return RCBF_E_BAD_SHAPE;  // a packet's grid is counted in work-items
+    const int32_t npkt = 2 * K;
+
+    auto* p = new rcbf_aql_plan();
+    p->q = q;
+    p->device = q->device;
+    p->K = K;
+    p->profiled = ends ? 2 : 0;
+    // the one-entry action table of the k_safe_steps_term packets follows the argument blocks
+    const size_t table_off = (size_t)npkt * kArgStride;
+    std::vector<unsigned char> host(table_off + sizeof(const float*), 0);
+    int rc = (int)hipMalloc(&p->kernargs, host.size());
+    {
+        const float* const tab = u_rl_buf;
+        std::memcpy(host.data() + table_off, &tab, sizeof tab);
+    }
+    for (int32_t j = 0; j < K && !rc; ++j) {
+        PolicyStepArgs pa;
+        std::memset(&pa, 0, sizeof pa);
+        pa.packed = packed;
+        pa.n_o = n_o;
+        pa.n_u = n_u;
+        pa.H = hidden;
+        pa.B = B;
+        // the observation step j - 1 left: its row of a recorded obs array, else the buffer every step overwrites
+        pa.obs = j == 0 ? obs_in : row_obs ? rows_on(obs_out, (int64_t)j - 1, row_obs) : obs_out;
+        pa.u_rl = u_rl_buf;
+        pa.seed = policy_seed;
+        pa.counter_word = counter_word;
+        pa.counter_add = (uint64_t)j;
+        pa.env_offset = policy_env_offset;
+        std::memcpy(host.data() + (size_t)(2 * j) * kArgStride, &pa, sizeof pa);
+        unsigned char* const dst = host.data() + (size_t)(2 * j + 1) * kArgStride;
+        if (term) {
+            SafeStepsTermArgs ea;
+            std::memset(&ea, 0, sizeof ea);
+            SafeStepsTrajArgs& ta = ea.t;
+            SafeStepsArgs& a = ta.s;
+            ea.term_obs = rows_on(term_obs, j, row_term);
+            ta.traj_mask = traj_mask;
+            ta.traj_pitch = traj_pitch;
+            io.fill(a, j);
+            // one step, its action the table's only entry
+            a.u_tab = reinterpret_cast<const float* const*>(static_cast<unsigned char*>(p->kernargs) + table_off);
+            a.n_u = 1;
+            a.steps = 1;
+            a.ju0 = 0;
+            std::memcpy(dst, &ea, sizeof ea);
+        } else {
+            SafeStepArgs a;
+            io.fill(a, j);
+            a.u_rl = u_rl_buf;
+            std::memcpy(dst, &a, sizeof a);
+        }
+    }
+    if (!rc) rc = (int)hipMemcpy(p->kernargs, host.data(), host.size(), hipMemcpyHostToDevice);
+    // ends: a signal on the first packet and one on the last; else one, on the last
+    for (int j = 0; !rc && j < (ends ? 2 : 1); ++j) {
+        hsa_signal_t s;
+        rc = hsa_rc(hsa_signal_create(1, 0, nullptr, &s));
+        if (!rc) p->sig.push_back(s);
+    }
+    if (rc) {
+        rcbf_aql_plan_free(p);
+        return rc;
+    }
+    p->pkt.resize(npkt);
+    for (int32_t j = 0; j < npkt; ++j) {
+        const bool is_policy = (j & 1) == 0;
+        const KernelInfo* kd = is_policy ? kp : ks;
+        hsa_kernel_dispatch_packet_t& d = p->pkt[j];
+        std::memset(&d, 0, sizeof d);
+        // the fences of the per-step form: agent scope between packets (the action and the observation pass
+        // through memory from one packet to the next), system-scope release on the last
+        const int acq =
+            j == 0 && (flags & RCBF_AQL_FIRST_ACQUIRE_SYSTEM) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
+        const int rel =
+            j == npkt - 1 && !(flags & RCBF_AQL_LAST_RELEASE_AGENT) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
+        d.header = (uint16_t)((HSA_PACKET_TYPE_KERNEL_DISPATCH << HSA_PACKET_HEADER_TYPE) |
+                              (1 << HSA_PACKET_HEADER_BARRIER) | (acq << HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) |
+                              (rel << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE));
+        d.setup = (uint16_t)(1 << HSA_KERNEL_DISPATCH_PACKET_SETUP_DIMENSIONS);
+        d.workgroup_size_x = (uint16_t)(is_policy ? 256 : bs);
+        d.workgroup_size_y = 1;
+        d.workgroup_size_z = 1;
+        d.grid_size_x = (uint32_t)(is_policy ? policy_groups * 256u : step_groups * (uint64_t)bs);
+        d.grid_size_y = 1;
+        d.grid_size_z = 1;
+        d.private_segment_size = kd->private_bytes;
+        d.group_segment_size = is_policy ? (uint32_t)policy_lds : kd->group_bytes;
+        d.kernel_object = kd->object;
+        d.kernarg_address = static_cast<unsigned char*>(p->kernargs) + (size_t)j * kArgStride;
+        if (j == npkt - 1)
+            d.completion_signal = p->sig.back();
+        else if (ends && j == 0)
+            d.completion_signal = p->sig.front();
+        else
+            d.completion_signal.handle = 0;
+    }
+    *out = p;
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {
@@ -813,6 +1118,13 @@ int rcbf_aql_plan_times(const rcbf_aql_plan* p, uint64_t* start_end_ns) {
             sg = p->sig[j];  // a per-dispatch profile is always the per-step form: packet j is step j
         }
         if (hsa_amd_profiling_get_dispatch_time(p->q->agent, sg, &t) != HSA_STATUS_SUCCESS) return RCBF_E_HSA;
+        if (p->profiled == 2 && p->K == 1 && p->sig.size() > 1) {
+            // a one-step closed-loop plan: the row is its two packets', the policy's start to the step's end
+            hsa_amd_profiling_dispatch_time_t t2;
+            if (hsa_amd_profiling_get_dispatch_time(p->q->agent, p->sig.back(), &t2) != HSA_STATUS_SUCCESS)
+                return RCBF_E_HSA;
+            t.end = t2.end;
+        }
         start_end_ns[2 * j] = (uint64_t)((long double)t.start * 1e9L / (long double)freq);
         start_end_ns[2 * j + 1] = (uint64_t)((long double)t.end * 1e9L / (long double)freq);
     }

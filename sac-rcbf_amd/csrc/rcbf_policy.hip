@@ -26,7 +26,12 @@
 // order, so a wave's weight load is one contiguous 256-B (W1) or 1-KiB (W2,
 // four k-steps per lane) read from L2; W2 is never held in LDS.  Rows past B
 // are computed on the last row's data and not stored: no conditional loads.
+//
+// Two kernel families share the body (policy_tile): k_policy_act, which rcbf_policy_act launches through HIP, and
+// rcbf::k_policy_step, which no HIP launch uses: csrc/rcbf_aql.hip dispatches it from librcbf_policy.co, this
+// file's gfx950 code object, as the policy packets of a closed-loop plan (rcbf_aql_closed_loop_plan).
 #include "rcbf_common.hpp"
+#include "rcbf_policy_step.hpp"
 
 using namespace rcbf;
 
@@ -56,10 +61,6 @@ inline PolicyLayout policy_layout(int n_o, int n_u, int H) {
     return L;
 }
 
-inline bool policy_shape_ok(int n_o, int n_u, int H) {
-    return n_o >= 1 && n_o <= 16 && n_u >= 1 && n_u <= 2 && H >= 32 && H <= 256 && H % 32 == 0;
-}
-
 // the accumulator of unit block cb starts as the bias: register r of lane half h holds unit
 // 32 cb + (r & 3) + 8 (r >> 2) + 4 h (the C/D row map), i.e. four float4 of the bias vector
 __device__ __forceinline__ f32x16 bias_acc(const float* __restrict__ b, int cb, int half) {
@@ -85,11 +86,13 @@ __device__ __forceinline__ void store_relu(float* s, const f32x16& a, int cb, in
     }
 }
 
+// The forward of one tile: the body of both kernel families (k_policy_act below, rcbf::k_policy_step after the
+// anonymous namespace).
 template <bool SAMPLE, int NRB>
-__global__ void __launch_bounds__(256) k_policy_act(const float* __restrict__ packed, int n_o, int n_u, int H,
-                                                    int64_t B, const float* __restrict__ obs,
-                                                    float* __restrict__ u_rl, const float* __restrict__ z,
-                                                    uint64_t seed, uint64_t counter, int64_t env_offset) {
+__device__ __forceinline__ void policy_tile(const float* __restrict__ packed, int n_o, int n_u, int H, int64_t B,
+                                            const float* __restrict__ obs, float* __restrict__ u_rl,
+                                            const float* __restrict__ z, uint64_t seed, uint64_t counter,
+                                            int64_t env_offset) {
     constexpr int ROWS = 32 * NRB;
     extern __shared__ __align__(16) float pol_smem[];
     float* const s_x = pol_smem;             // [16][ROWS]   obs^T, zero column when n_o is odd
@@ -228,7 +231,13 @@ __global__ void __launch_bounds__(256) k_policy_act(const float* __restrict__ pa
     }
 }
 
-inline size_t policy_lds_bytes(int H, int nrb) { return (size_t)(16 + 2 * H + 4) * 32 * nrb * sizeof(float); }
+template <bool SAMPLE, int NRB>
+__global__ void __launch_bounds__(256) k_policy_act(const float* __restrict__ packed, int n_o, int n_u, int H,
+                                                    int64_t B, const float* __restrict__ obs,
+                                                    float* __restrict__ u_rl, const float* __restrict__ z,
+                                                    uint64_t seed, uint64_t counter, int64_t env_offset) {
+    policy_tile<SAMPLE, NRB>(packed, n_o, n_u, H, B, obs, u_rl, z, seed, counter, env_offset);
+}
 
 template <bool SAMPLE, int NRB>
 int policy_launch(const float* packed, int n_o, int n_u, int H, int64_t B, const float* obs, float* u_rl,
@@ -253,6 +262,36 @@ int policy_launch(const float* packed, int n_o, int n_u, int H, int64_t B, const
 }
 
 }  // namespace
+
+namespace rcbf {
+
+// The policy packet of a closed-loop AQL plan (PolicyStepArgs, rcbf_policy_step.hpp): k_policy_act with the draw
+// counter read from a device word when the packet runs -- a plan's argument blocks are written once, and every
+// run must draw fresh noise -- plus the packet's own offset (its step index).  In-kernel draws only: no z.
+// External linkage in namespace rcbf, like k_safe_step: rcbf_aql_open finds the kernels by their mangled names.
+template <bool SAMPLE, int NRB>
+__global__ void __launch_bounds__(256) k_policy_step(const float* __restrict__ packed, int n_o, int n_u, int H,
+                                                     int64_t B, const float* __restrict__ obs,
+                                                     float* __restrict__ u_rl, uint64_t seed,
+                                                     const uint64_t* __restrict__ counter_word, uint64_t counter_add,
+                                                     int64_t env_offset) {
+    uint64_t counter = counter_add;
+    if constexpr (SAMPLE) {
+        if (counter_word) counter += *counter_word;
+    }
+    policy_tile<SAMPLE, NRB>(packed, n_o, n_u, H, B, obs, u_rl, nullptr, seed, counter, env_offset);
+}
+
+template __global__ void k_policy_step<false, 1>(const float*, int, int, int, int64_t, const float*, float*, uint64_t,
+                                                 const uint64_t*, uint64_t, int64_t);
+template __global__ void k_policy_step<false, 2>(const float*, int, int, int, int64_t, const float*, float*, uint64_t,
+                                                 const uint64_t*, uint64_t, int64_t);
+template __global__ void k_policy_step<true, 1>(const float*, int, int, int, int64_t, const float*, float*, uint64_t,
+                                                const uint64_t*, uint64_t, int64_t);
+template __global__ void k_policy_step<true, 2>(const float*, int, int, int, int64_t, const float*, float*, uint64_t,
+                                                const uint64_t*, uint64_t, int64_t);
+
+}  // namespace rcbf
 
 extern "C" int64_t rcbf_policy_packed_floats(int32_t n_o, int32_t n_u, int32_t hidden) {
     if (!policy_shape_ok(n_o, n_u, hidden)) return -1;

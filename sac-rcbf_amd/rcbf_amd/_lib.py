@@ -132,6 +132,11 @@ SIGNATURES = {
     "rcbf_aql_safe_step_term_plan": [_P, _PRM, _I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _I32, _U64, _I64, _P, _I32, _I32, _I64, _P,
                                      ctypes.POINTER(ctypes.c_void_p)],
+    # a closed-loop plan: the term plan's arguments with ONE action buffer in place of (u_rl_seq, n_u_rl), then
+    # obs_in, packed, n_o, n_u, hidden, mode, policy seed, counter_word, policy env_offset
+    "rcbf_aql_closed_loop_plan": [_P, _PRM, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, _I32, _U64, _I64, _P, _I32, _I32, _I64, _P, _P, _P, _I32, _I32, _I32, _I32,
+                                  _U64, _P, _I64, ctypes.POINTER(ctypes.c_void_p)],
     # a trajectory's K B transitions into the replay ring: ring, capacity, position, B, K, P, n_o, n_u, obs0,
     # step0, obs, term_obs, u, reward, done, max_episode_steps, dt, auto_reset, stream
     "rcbf_traj_pack_replay_f64": [_P, _I64, _I64, _I64, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32,

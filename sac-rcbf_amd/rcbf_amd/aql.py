@@ -31,6 +31,14 @@ fused (the k_safe_steps_term kernels, K = 1 included): where it would have to
 be per-step, safe_step_plan raises.  `ReplayMemory.push_trajectory` packs the
 result into replay records.
 
+A CLOSED-LOOP plan (`AqlQueue.closed_loop_plan(env, policy, layer, K, ...)`)
+is for the steps whose actions are NOT known beforehand: a DevicePolicy
+computes step j's action from the observation step j - 1 left.  It is 2K
+packets, the policy's kernel (rcbf::k_policy_step, librcbf_policy.co) before
+every step, with the fences of the per-step form; it records trajectories
+("term_obs" included) like the plans above, and everything is bit for bit what
+K times policy.act() then env.safe_step() compute through the HIP launch path.
+
 The queue is not a HIP stream: `run()` first waits for all HIP work queued
 on the env's device unless `sync_hip=False` is
 passed by a caller that has synchronised itself (bench.py's timed region
@@ -176,6 +184,88 @@ class AqlQueue:
         self._plans.add(plan)
         return plan
 
+    def closed_loop_plan(self, env, policy, layer, steps, evaluate=False, mean=None, sigma=None, outputs=None,
+                         auto_reset=True, prior_layout="rows", trajectory=None, fence_flags=0):
+        """K = steps closed-loop steps of `env`: before step j the policy
+        (a DevicePolicy) computes the action from the observation step j - 1
+        left, as policy.act(env.obs, evaluate, out=u) followed by
+        env.safe_step(u, layer, mean, sigma, ...) does, K times, but as 2K
+        packets behind one doorbell (rcbf_aql_closed_loop_plan).  Returns a
+        ClosedLoopPlan (an AqlPlan): `plan.u_rl` is the (B, n_u) action
+        buffer the plan owns (after a run, the last step's policy action);
+        `plan.dispatches` is 2K.  trajectory: as in safe_step_plan, "term_obs"
+        included (exact solver only).  evaluate=False samples with the
+        in-kernel draws of (policy.seed, policy.env_offset + row, counter), the
+        counter set per run (ClosedLoopPlan.run).  policy.refresh() between
+        runs is seen by the next run: the plan reads the policy's packed
+        buffer, whose address does not change.  fence_flags: the fence scopes
+        and PROFILE_ENDS (on a queue opened with profile=True)."""
+        from .policy import DevicePolicy
+        if env.device != self.device:
+            raise ValueError(f"env on {env.device}, queue on {self.device}")
+        if not isinstance(policy, DevicePolicy):
+            raise ValueError("a closed-loop plan needs a DevicePolicy: its packed weights are what the packets read")
+        if policy.device != env.device:
+            raise ValueError(f"the policy is on {policy.device}, the env on {env.device}")
+        if (policy.n_o, policy.n_u) != (env.n_o, env.n_u):
+            raise ValueError(f"the policy maps {policy.n_o} observations to {policy.n_u} actions, the env has "
+                             f"{env.n_o} and {env.n_u}")
+        if not evaluate and not policy.has_log_std:
+            raise NotImplementedError("evaluate=False needs a log-std head: the reference's DeterministicPolicy.sample "
+                                      "shares one noise vector across rows, which is not reproduced")
+        K = int(steps)
+        if K <= 0:
+            raise ValueError(f"steps must be positive, got {steps}")
+        flags = int(fence_flags)
+        if flags & (PROFILE | 8 | 16 | 32):
+            raise ValueError("a closed-loop plan takes no per-dispatch profile and no study fences "
+                             "(PROFILE_ENDS times it end to end)")
+        if flags & PROFILE_ENDS and not self.profile:
+            raise ValueError("PROFILE_ENDS needs a queue opened with profile=True")
+        if prior_layout not in ("rows", "cols"):
+            raise ValueError(f"prior_layout must be 'rows' or 'cols', got {prior_layout!r}")
+        cols = prior_layout == "cols"
+        if cols:
+            if mean is not None and env.dynamics_mode == "SimulatedCars":
+                raise ValueError("the cars CBF rows read no mean (diff_cbf_qp.py:298-299): pass mean=None")
+            mean, sigma = env._prior_cols_arg(mean, "mean"), env._prior_cols_arg(sigma, "sigma")
+        else:
+            mean, sigma = env._prior_arg(mean, "mean"), env._prior_arg(sigma, "sigma")
+        o = outputs if outputs is not None else env.make_outputs()
+        a = env._step_args(layer, o, auto_reset)
+        outs = list(a[9:17])
+        traj, mask, pitch, term = None, 0, 0, None
+        if trajectory is not None and trajectory is not False:
+            traj = env.make_trajectory(K) if trajectory is True else dict(trajectory)
+            mask, pitch = _trajectory_args(env, traj, K)
+            term = traj.get("term_obs")
+            if term is not None:
+                if layer._prm.solver != _lib.SOLVER_ACTIVE_SET:
+                    raise ValueError("a plan that records term_obs needs the exact active-set solver, but the "
+                                     "layer's solver is another")
+                mask |= TRAJ_TERM_OBS
+            for j, f in enumerate(("obs", "u", "reward", "cost", "done", "goal_met", "status")):
+                if mask & TRAJ_BITS[f]:
+                    outs[j] = traj[f].data_ptr()
+        u_rl = torch.zeros(env.num_envs, env.n_u, dtype=torch.float32, device=env.device)
+        # the draw counter of a sampling plan: one device word, set by run() before the doorbell
+        word = None if evaluate else torch.zeros(1, dtype=torch.int64, device=env.device)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(_lib.load().rcbf_aql_closed_loop_plan(
+                self.handle, ctypes.byref(layer._prm), env.num_envs, K, *[v or None for v in a[2:6]], u_rl.data_ptr(),
+                None if mean is None else mean.data_ptr(), None if sigma is None else sigma.data_ptr(), int(cols),
+                *[v or None for v in outs], *a[17:20], None, flags, mask, pitch,
+                None if term is None else term.data_ptr(), env.obs.data_ptr(), policy.packed.data_ptr(), policy.n_o,
+                policy.n_u, policy.hidden, _lib.POLICY_MEAN if evaluate else _lib.POLICY_SAMPLE,
+                policy.seed & 0xFFFFFFFFFFFFFFFF, None if word is None else word.data_ptr(), policy.env_offset,
+                ctypes.byref(h)), "rcbf_aql_closed_loop_plan")
+        # the plan holds raw pointers: keep every tensor it reads or writes alive with it
+        keep = (env, layer, o, u_rl, mean, sigma, None, traj, policy, policy.packed, word)
+        plan = ClosedLoopPlan(self, h, K, keep, env, traj, policy, u_rl, word)
+        self._plans.add(plan)
+        return plan
+
 
 def _trajectory_args(env, traj, K):
     """(traj_mask, traj_pitch) of a trajectory dict for a K-step plan of
@@ -282,3 +372,44 @@ class AqlPlan:
 
     def free(self):
         self._fin()
+
+
+class ClosedLoopPlan(AqlPlan):
+    """K closed-loop steps, policy and safe step alternating (see
+    AqlQueue.closed_loop_plan).  `u_rl`: the plan's (B, n_u) action buffer."""
+
+    def __init__(self, queue, handle, K, keep, env, trajectory, policy, u_rl, word):
+        super().__init__(queue, handle, K, keep, False, env, trajectory)
+        self.policy, self.u_rl, self._word = policy, u_rl, word
+
+    @property
+    def sampling(self):
+        return self._word is not None
+
+    def run(self, counter=None, sync_hip=True, timeout_us=0, copy_back=True):
+        """AqlPlan.run.  A sampling plan's K steps draw with the counters
+        c, c + 1, ..., c + K - 1: c = `counter`, or, when that is None,
+        policy._counter, which then advances by K -- plans and policy.act()
+        calls interleave without repeating a draw.  c is written to the
+        plan's device word on the current stream, and the stream is
+        synchronised before the doorbell (with sync_hip=False too, which skips
+        only the device-wide synchronise), so packet 0 finds it there.  When
+        obs is recorded, row K - 1 always goes back to env.obs, copy_back=False
+        included: the next run's first packet reads env.obs."""
+        dev = self.queue.device
+        if self._word is not None:
+            c = self.policy._counter if counter is None else int(counter)
+            if counter is None:
+                self.policy._counter += self.K
+            c &= 0xFFFFFFFFFFFFFFFF
+            with torch.cuda.device(dev):
+                self._word.fill_(c - (1 << 64) if c >= 1 << 63 else c)
+        elif counter is not None:
+            raise ValueError("counter is the sampling plans' draw counter: this plan was built with evaluate=True")
+        if not sync_hip:
+            # the word's fill and the last run's copy into env.obs are on the current stream
+            torch.cuda.current_stream(dev).synchronize()
+        out = super().run(sync_hip=sync_hip, timeout_us=timeout_us, copy_back=copy_back)
+        if self.trajectory is not None and not copy_back and "obs" in self.trajectory:
+            self._env.obs.copy_(self.trajectory["obs"][self.K - 1])
+        return out

@@ -6,7 +6,9 @@ agent.select_action(obs, evaluate=True) -> env.step, summing reward and cost
 until the episode ends, and the averages over the episodes.  Here the B envs
 of a Batched*Env are the episodes: DevicePolicy.act (one launch) feeds
 env.safe_step (one launch), EpisodeStats keeps the sums, and the host reads
-once, after the last step.
+once, after the last step.  With an AqlQueue the steps run as closed-loop AQL
+plans instead (AqlQueue.closed_loop_plan: the policy's packet before every
+step's, one doorbell per chunk of steps) and the host reads once per chunk.
 """
 import numpy as np
 import torch
@@ -14,7 +16,7 @@ import torch
 from .episode_stats import EpisodeStats
 
 
-def evaluate_policy(env, policy, layer, steps=None, mean=None, sigma=None, evaluate=True):
+def evaluate_policy(env, policy, layer, steps=None, mean=None, sigma=None, evaluate=True, queue=None, chunk=None):
     """Run `steps` (default env.max_episode_steps) closed-loop steps of
     policy.act(env.obs) -> env.safe_step(u, layer, mean, sigma) from a reset and
     return, over each env's FIRST finished episode,
@@ -25,7 +27,13 @@ def evaluate_policy(env, policy, layer, steps=None, mean=None, sigma=None, evalu
     No host synchronisation inside the loop: one read at the end, then
     env.check_failures().  A step is the two kernels, the three launches of
     EpisodeStats.update and nine small torch launches that keep each env's
-    first record."""
+    first record.
+    queue: an AqlQueue on the env's device.  The steps then run as closed-loop
+    AQL plans (AqlQueue.closed_loop_plan) of `chunk` steps (default
+    min(steps, 256); the last one shorter when chunk does not divide steps)
+    that record reward, cost and done: one doorbell and one
+    EpisodeStats.update per chunk, each env's first record picked on the host.
+    The same dict, bit for bit."""
     steps = int(env.max_episode_steps if steps is None else steps)
     if steps <= 0:
         raise ValueError(f"steps must be positive, got {steps}")
@@ -41,8 +49,55 @@ def evaluate_policy(env, policy, layer, steps=None, mean=None, sigma=None, evalu
         raise ValueError(f"the policy is on {policy.device}, the env on {dev}")
     if dev.type != "cuda":
         raise ValueError("evaluate_policy needs a device env")
+    if queue is not None:
+        if chunk is not None and int(chunk) <= 0:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+        env.reset()
+        return _evaluate_plans(env, policy, layer, steps, mean, sigma, evaluate, queue, chunk)
+    if chunk is not None:
+        raise ValueError("chunk is the plan length of the queue path: pass queue as well")
     env.reset()
     return _evaluate_from(env, policy, layer, steps, mean, sigma, evaluate)
+
+
+def _evaluate_plans(env, policy, layer, steps, mean=None, sigma=None, evaluate=True, queue=None, chunk=None):
+    """evaluate_policy's loop from the env's current state as closed-loop
+    plans (arguments already checked).  The episode sums carry from one
+    update to the next, so the records are those of the per-step loop."""
+    B = int(env.num_envs)
+    chunk = min(steps, 256 if chunk is None else int(chunk))
+    stats = EpisodeStats(env)  # lengths start from env.step_count
+    o = env.make_outputs()
+    traj = env.make_trajectory(chunk, ("reward", "cost", "done"))
+    full, rest = divmod(steps, chunk)
+    kw = dict(evaluate=evaluate, mean=mean, sigma=sigma, outputs=o)
+    plans = [(queue.closed_loop_plan(env, policy, layer, chunk, trajectory=traj, **kw), full)]
+    if rest:
+        plans.append((queue.closed_loop_plan(env, policy, layer, rest,
+                                             trajectory={f: t[:rest] for f, t in traj.items()}, **kw), 1))
+    reward, cost = np.full(B, np.nan), np.full(B, np.nan)
+    length, have = np.zeros(B, np.int32), np.zeros(B, bool)
+    try:
+        for plan, runs in plans:
+            for _ in range(runs):
+                plan.run()
+                rec = stats.update(plan.trajectory, rows=plan.K)  # exact: an env may finish several episodes
+                e = rec["env"].cpu().numpy()
+                r, c, n = rec["reward"].cpu().numpy(), rec["cost"].cpu().numpy(), rec["length"].cpu().numpy()
+                # the records come in step order: the first row of an env without a record yet is its first
+                idx = np.unique(e, return_index=True)[1]
+                idx = idx[~have[e[idx]]]
+                reward[e[idx]], cost[e[idx]], length[e[idx]] = r[idx], c[idx], n[idx]
+                have[e[idx]] = True
+    finally:
+        for plan, _ in plans:
+            plan.free()
+    n = int(have.sum())
+    out = {"avg_reward": float(reward[have].mean()) if n else float("nan"),
+           "avg_cost": float(cost[have].mean()) if n else float("nan"),
+           "episodes": n, "reward": reward, "cost": cost, "length": length}
+    env.check_failures()
+    return out
 
 
 def _evaluate_from(env, policy, layer, steps, mean=None, sigma=None, evaluate=True):
