@@ -664,6 +664,12 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
  * no u_RL buffer overlaps a buffer the steps write (the fused kernel loads
  * the next step's action before the current step's stores), and the code
  * object has the fused kernels; otherwise the per-step form.
+ * A fused plain plan of the cars env runs k_safe_steps_fast (librcbf_steps_fast.co,
+ * csrc/rcbf_safe_steps_fast.hpp: the same argument block, the same stores and
+ * bits, a loop laid out for the instruction scheduler) in k_safe_steps's place
+ * when B % 64 == 0, obs_out is 16-byte aligned, goal_met and status_out are
+ * NULL and episode and fail_flag are not; RCBF_AQL_FUSED_LOOP keeps k_safe_steps.
+ * rcbf_aql_plan_form says which kernel a plan took (RCBF_AQL_FORM_*).
  * rcbf_aql_plan_dispatches: dispatch packets per run (K, or the chunks).
  * rcbf_aql_run: submit the K dispatches (barrier bit on each), ring the
  * doorbell once, busy-wait for completion; timeout_us 0 -> 10 s.  A plan
@@ -790,6 +796,11 @@ int rcbf_safe_rollout(const rcbf_params* prm, int64_t B, int32_t K, double* x, d
 #define RCBF_AQL_STUDY_MID_NOREL 32     /* STUDY ONLY: no release between steps */
 #define RCBF_AQL_PROFILE_ENDS 64        /* timestamps of the first and the last dispatch only */
 #define RCBF_AQL_PER_STEP 128           /* build the per-step form (K dispatches) even where the fused form applies */
+#define RCBF_AQL_FUSED_LOOP 256         /* a fused cars plan keeps k_safe_steps where k_safe_steps_fast applies */
+/* rcbf_aql_plan_form: the kernel a plan's step packets dispatch */
+#define RCBF_AQL_FORM_PER_STEP 0   /* k_safe_step, one packet per step */
+#define RCBF_AQL_FORM_FUSED 1      /* k_safe_steps / k_safe_steps_traj / k_safe_steps_term */
+#define RCBF_AQL_FORM_FUSED_FAST 2 /* k_safe_steps_fast: the cars fused plan's straight-line loop */
 #define RCBF_AQL_SAFE_STEP_KERNARG_BYTES 408 /* sizeof the k_safe_step argument block */
 #define RCBF_AQL_SAFE_STEPS_KERNARG_BYTES 408 /* sizeof the k_safe_steps (fused form) argument block */
 #define RCBF_AQL_SAFE_STEPS_TRAJ_KERNARG_BYTES 424 /* ... of k_safe_steps_traj: + traj_mask (408), traj_pitch (416) */
@@ -832,6 +843,7 @@ int rcbf_aql_closed_loop_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, in
 int rcbf_aql_run(rcbf_aql_plan* plan, uint64_t timeout_us);
 int rcbf_aql_plan_times(const rcbf_aql_plan* plan, uint64_t* start_end_ns);
 int rcbf_aql_plan_dispatches(const rcbf_aql_plan* plan);
+int rcbf_aql_plan_form(const rcbf_aql_plan* plan);
 int rcbf_aql_plan_free(rcbf_aql_plan* plan);
 
 /* ---------------------------------------------------------------------- */

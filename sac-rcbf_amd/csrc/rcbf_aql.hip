@@ -152,13 +152,17 @@ struct rcbf_aql {
     hsa_code_object_reader_t reader_policy{};  // librcbf_policy.co (the k_policy_step kernels), if there
     hsa_executable_t exe_policy{};
     bool have_reader_policy = false, have_exe_policy = false;
-    std::vector<char> code, code_traj, code_term, code_policy;
+    hsa_code_object_reader_t reader_fast{};  // librcbf_steps_fast.co (the k_safe_steps_fast kernels), if there
+    hsa_executable_t exe_fast{};
+    bool have_reader_fast = false, have_exe_fast = false;
+    std::vector<char> code, code_traj, code_term, code_policy, code_fast;
     std::vector<KernelInfo> kernels;
     std::atomic<int> queue_error{0};
     int profiling = 0;
     bool fused = false;  // the code object has the k_safe_steps kernels (the fused plan form)
     bool traj = false;   // ... and the k_safe_steps_traj kernels (the fused form of a trajectory plan)
     bool term = false;   // ... and the k_safe_steps_term kernels (trajectory plans with RCBF_TRAJ_TERM_OBS)
+    bool fast = false;   // ... and the three k_safe_steps_fast kernels (the cars fused plan's straight-line loop)
     bool policy = false;  // the four k_policy_step kernels were found, each taking PolicyStepArgs (closed-loop plans)
 };
 
@@ -171,6 +175,7 @@ struct rcbf_aql_plan {
     std::vector<hsa_signal_t> sig;                  // completion signals: one per packet (profiled), first and
                                                     // last (ends; one if they are the same packet), or one
     int profiled = 0;
+    int form = RCBF_AQL_FORM_PER_STEP;  // RCBF_AQL_FORM_*: the kernel its step packets dispatch
 };
 
 namespace {
@@ -254,6 +259,13 @@ std::string safe_steps_traj_prefix(int mode, int k, int bs) {
 std::string safe_steps_term_prefix(int mode, int k, int bs) {
     char buf[128];
     snprintf(buf, sizeof buf, "_ZN4rcbf17k_safe_steps_termILi%dELi%dELi%dEEEv", mode, k, bs);
+    return buf;
+}
+
+// ... and of rcbf::k_safe_steps_fast<BS> (SafeStepsArgs)
+std::string safe_steps_fast_prefix(int bs) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "_ZN4rcbf17k_safe_steps_fastILi%dEEEv", bs);
     return buf;
 }
 
@@ -393,6 +405,8 @@ void destroy(rcbf_aql* q) {
     if (q->have_exe_traj) hsa_executable_destroy(q->exe_traj);
     if (q->have_exe_term) hsa_executable_destroy(q->exe_term);
     if (q->have_exe_policy) hsa_executable_destroy(q->exe_policy);
+    if (q->have_exe_fast) hsa_executable_destroy(q->exe_fast);
+    if (q->have_reader_fast) hsa_code_object_reader_destroy(q->reader_fast);
     if (q->have_reader_policy) hsa_code_object_reader_destroy(q->reader_policy);
     if (q->have_reader) hsa_code_object_reader_destroy(q->reader);
     if (q->have_reader_traj) hsa_code_object_reader_destroy(q->reader_traj);
@@ -449,6 +463,11 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     }
     // ... and the policy kernels of the closed-loop plans (librcbf_policy.co): without it those plans are refused
     if (!read_optional_code_object(policy_code_object_path(path), q->code_policy)) {
+        delete q;
+        return RCBF_E_BAD_SHAPE;
+    }
+    // ... and NAME_fast.co, the cars fused plan's straight-line loop: without it those plans take k_safe_steps
+    if (!read_side_code_object(path, "_fast", q->code_fast)) {
         delete q;
         return RCBF_E_BAD_SHAPE;
     }
@@ -523,6 +542,20 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
         if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_policy, nullptr));
         if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_policy, q->agent, collect_kernel, q));
     }
+    if (!rc && !q->code_fast.empty()) {
+        rc = hsa_rc(
+            hsa_code_object_reader_create_from_memory(q->code_fast.data(), q->code_fast.size(), &q->reader_fast));
+        if (!rc) q->have_reader_fast = true;
+        if (!rc)
+            rc = hsa_rc(hsa_executable_create_alt(HSA_PROFILE_FULL, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr,
+                                                  &q->exe_fast));
+        if (!rc) q->have_exe_fast = true;
+        if (!rc)
+            rc = hsa_rc(
+                hsa_executable_load_agent_code_object(q->exe_fast, q->agent, q->reader_fast, nullptr, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_freeze(q->exe_fast, nullptr));
+        if (!rc) rc = hsa_rc(hsa_executable_iterate_agent_symbols(q->exe_fast, q->agent, collect_kernel, q));
+    }
     // every k_safe_step instantiation in the code object must take exactly the
     // argument block SafeStepArgs describes
     // ... and every k_safe_steps instantiation SafeStepsArgs; a code object without them still opens, and
@@ -547,6 +580,14 @@ int rcbf_aql_open(int32_t device, const char* code_object_path, int32_t flags, r
     q->fused = n_fused > 0;
     q->traj = n_traj > 0;
     q->term = n_term > 0;
+    // the straight-line cars loop, at the three workgroup sizes: all three, each taking SafeStepsArgs and no
+    // scratch, or no plan takes it (nothing else is affected)
+    int n_fast = 0;
+    for (int bs : {64, 128, 256}) {
+        const KernelInfo* kp = find_kernel(q, safe_steps_fast_prefix(bs));
+        if (kp && kp->kernarg_bytes == sizeof(SafeStepsArgs) && kp->private_bytes == 0) ++n_fast;
+    }
+    q->fast = n_fast == 3;
     // the closed-loop plans' policy kernels, {mean, sample} x {32-row, 64-row tiles}: all four, each taking
     // PolicyStepArgs and no scratch, or no closed-loop plan is built on this queue (nothing else is affected)
     int n_policy = 0;
@@ -687,6 +728,20 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
                     break;
                 }
     }
+    // The cars fused plan's straight-line loop (k_safe_steps_fast, rcbf_safe_steps_fast.hpp) in k_safe_steps's
+    // place, same argument block and same results: a plain fused cars plan whose waves are all full and stage
+    // their rows through LDS (B % 64 == 0, a 16-byte aligned observation buffer), with the optional buffers as
+    // BatchedEnv passes them for cars (no goal_met, no status_out; episode and fail_flag).  Anything else, a code
+    // object without those kernels, and RCBF_AQL_FUSED_LOOP take k_safe_steps as before.
+    bool fast = false;
+    if (kf && q->fast && cars && !term && !traj_mask && K > 1 && B % 64 == 0 && !(((uintptr_t)obs_out) & 15) &&
+        !goal_met && !status_out && episode && fail_flag && !(flags & RCBF_AQL_FUSED_LOOP)) {
+        const KernelInfo* kfast = find_kernel(q, safe_steps_fast_prefix(bs));
+        if (kfast && kfast->kernarg_bytes == sizeof(SafeStepsArgs)) {
+            kf = kfast;
+            fast = true;
+        }
+    }
     if (term && !kf) return RCBF_E_BAD_MODE;  // no per-step form keeps the terminal observation
     const int32_t npkt = kf ? (K + kFusedChunk - 1) / kFusedChunk : K;
 
@@ -695,6 +750,7 @@ static int build_safe_step_plan(rcbf_aql* q, const rcbf_params* prm, int64_t B, 
     p->device = q->device;
     p->K = K;
     p->profiled = ends ? 2 : profiled ? 1 : 0;
+    p->form = fast ? RCBF_AQL_FORM_FUSED_FAST : kf ? RCBF_AQL_FORM_FUSED : RCBF_AQL_FORM_PER_STEP;
     // the fused form's table of the n_u_rl action pointers follows the argument blocks
     const size_t table_off = (size_t)npkt * kArgStride;
     std::vector<unsigned char> host(table_off + (kf ? (size_t)n_u_rl * sizeof(const float*) : 0), 0);
@@ -1132,6 +1188,8 @@ int rcbf_aql_plan_times(const rcbf_aql_plan* p, uint64_t* start_end_ns) {
 }
 
 int rcbf_aql_plan_dispatches(const rcbf_aql_plan* p) { return p ? (int)p->pkt.size() : RCBF_E_NULL; }
+
+int rcbf_aql_plan_form(const rcbf_aql_plan* p) { return p ? p->form : RCBF_E_NULL; }
 
 int rcbf_aql_plan_free(rcbf_aql_plan* p) {
     if (!p) return 0;

@@ -245,8 +245,12 @@ __device__ __forceinline__ float div_f32_via_rcp(float a, double rb) { return (f
 // sin(x) for |x| <= 1.3 by its Taylor series to x^21 (truncation < 2e-19,
 // ~1 ulp rounding), else the library sin.  The cars lead-car term
 // sin(0.2 t) stays below 1.3 for t <= 6.5 s, i.e. within one 300-step episode.
+// POLY_ONLY (the straight-line fused loop, which has checked the range for its whole wave): the series alone.
+template <bool POLY_ONLY = false>
 __device__ __forceinline__ double sin_small(double x) {
-    if (!(fabs(x) <= 1.3)) return sin(x);
+    if constexpr (!POLY_ONLY) {
+        if (!(fabs(x) <= 1.3)) return sin(x);
+    }
     const double x2 = x * x;
     double p = -1.9572941063391263e-20;  // -1/21!
     p = fma(p, x2, 8.2206352466243297e-18);   // 1/19!
@@ -2052,11 +2056,13 @@ struct CarsStepOut {
 // before the layer's chain runs (RCBF_EARLY_STORE, the product default since
 // r03: 3.85 -> 3.67 us per step, profiles/r03/early_store_confirm_r03k.txt;
 // r01's first form of it measured no faster, profiles/r01/ablate_early_store.txt).
+// POLY_ONLY: sin_small's series for every lane (the caller knows |0.2 t| <= 1.3 in all of them).
+template <bool POLY_ONLY = false>
 __device__ __forceinline__ double cars_env_pre(const rcbf_params& prm, double* xs, double& t, int& step,
                                                CarsStepOut& o) {
 #pragma clang fp contract(off)
     const double kp = prm.kp, kb = prm.k_brake, dt = 0.02;
-    double vdes0 = 30.0 - 10.0 * sin_small(0.2 * t);
+    double vdes0 = 30.0 - 10.0 * sin_small<POLY_ONLY>(0.2 * t);
     double acc[5];
     acc[0] = kp * (vdes0 - xs[1]);
 #pragma unroll
@@ -2088,7 +2094,9 @@ __device__ __forceinline__ double cars_env_pre(const rcbf_params& prm, double* x
     return acc[3];
 }
 
-template <typename A>
+// RCP (the straight-line fused loop, fp32 actions only): the reward's division by 300 as div_f32_via_rcp, the
+// same fp32 bits by that function's argument (both operands are fp32; tests/test_fused_fast_isa_cpu.py sweeps it)
+template <typename A, bool RCP = false>
 __device__ __forceinline__ void cars_env_post(double* xs, double acc3, A action, CarsStepOut& o) {
 #pragma clang fp contract(off)
     const double dt = 0.02;
@@ -2096,6 +2104,13 @@ __device__ __forceinline__ void cars_env_post(double* xs, double acc3, A action,
     xs[7] += dt * (acc3 + gu);
     // reward in the action's dtype (-5.0 * abs(a**2) / 300), :93
     A a2 = action * action;
+    if constexpr (RCP) {
+        static_assert(sizeof(A) == 4, "div_f32_via_rcp: fp32 operands");
+        const float r = div_f32_via_rcp((float)((A)(-5.0) * (a2 < (A)0 ? -a2 : a2)), 1.0 / 300.0);
+        o.reward = r;
+        o.reward_d = (double)r;
+        return;
+    }
     A r = (A)(-5.0) * (a2 < (A)0 ? -a2 : a2) / (A)300;
     o.reward = (float)r;
     o.reward_d = (double)r;

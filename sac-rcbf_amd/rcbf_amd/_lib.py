@@ -157,6 +157,7 @@ SIGNATURES = {
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],
+    "rcbf_aql_plan_form": [_P],
     "rcbf_aql_plan_free": [_P],
     "rcbf_host_free": [_P],
     "rcbf_version": [],

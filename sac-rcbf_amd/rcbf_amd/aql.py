@@ -15,6 +15,11 @@ still stores everything a step stores), without the fence and the state
 re-load between two dispatches.  `plan.dispatches` tells which form a plan
 took (K: per step; 1 per 4096 steps: fused); `fused=False`, a span buffer,
 `profile=True` or a u_RL buffer that overlaps an output keep the per-step form.
+A fused plain plan of the cars env whose waves are all full (B % 64 == 0, the
+observation buffer 16-byte aligned) runs the straight-line loop
+(k_safe_steps_fast, csrc/rcbf_safe_steps_fast.hpp), bit for bit the same steps;
+`fast=False` keeps k_safe_steps, and `plan.form` names the kernel a plan took
+("per_step", "fused", "fused_fast").
 
 A TRAJECTORY plan (`trajectory=True`, or a dict from
 `BatchedEnv.make_trajectory`) keeps every step's outputs: step j writes row j
@@ -54,6 +59,8 @@ from . import _lib
 PROFILE = 1  # RCBF_AQL_PROFILE
 PROFILE_ENDS = 64  # RCBF_AQL_PROFILE_ENDS: timestamps of the first and last dispatch only
 PER_STEP = 128  # RCBF_AQL_PER_STEP: K dispatches even where the fused form applies
+FUSED_LOOP = 256  # RCBF_AQL_FUSED_LOOP: a fused cars plan keeps k_safe_steps where k_safe_steps_fast applies
+FORMS = ("per_step", "fused", "fused_fast")  # RCBF_AQL_FORM_*: AqlPlan.form
 # RCBF_TRAJ_*: the outputs a trajectory plan records
 TRAJ_OBS, TRAJ_U, TRAJ_REWARD, TRAJ_COST, TRAJ_DONE, TRAJ_GOAL_MET, TRAJ_STATUS = 1, 2, 4, 8, 16, 32, 64
 TRAJ_BITS = {"obs": TRAJ_OBS, "u": TRAJ_U, "reward": TRAJ_REWARD, "cost": TRAJ_COST, "done": TRAJ_DONE,
@@ -104,13 +111,15 @@ class AqlQueue:
 
     def safe_step_plan(self, env, u_rl_seq, layer, steps=None, mean=None, sigma=None, outputs=None,
                        auto_reset=True, prior_layout="rows", span=None, profile=False, fence_flags=0, fused=None,
-                       trajectory=None):
+                       trajectory=None, fast=None):
         """K = steps (default len(u_rl_seq)) fused safe steps of `env` with
         `layer`, step j reading u_rl_seq[j % len(u_rl_seq)]: the same
         arguments and results as env.safe_step_seq (span: the measurement
         instantiation of env.safe_step_span, step j stamping span[j]).
         fused: None or True leave the plan's form to the library (fused where
         it applies, see the module docstring); False asks for K dispatches.
+        fast: None or True leave the fused cars plan's kernel to the library;
+        False keeps k_safe_steps (RCBF_AQL_FUSED_LOOP).
         trajectory: None (a plain plan), True (record every field of
         env.TRAJECTORY_FIELDS, allocated here) or a dict of (K', B[, w])
         views, K' >= K, of pitch-padded arrays as env.make_trajectory
@@ -144,7 +153,8 @@ class AqlQueue:
         a = env._step_args(layer, o, auto_reset)
         arr = (ctypes.c_void_p * len(us))(*[u.data_ptr() for u in us])
         h = ctypes.c_void_p()
-        flags = (PROFILE if profile else 0) | (PER_STEP if fused is False else 0) | int(fence_flags)
+        flags = ((PROFILE if profile else 0) | (PER_STEP if fused is False else 0) |
+                 (FUSED_LOOP if fast is False else 0) | int(fence_flags))
         head = (self.handle, ctypes.byref(layer._prm), env.num_envs, K, *[v or None for v in a[2:6]], arr, len(us),
                 None if mean is None else mean.data_ptr(), None if sigma is None else sigma.data_ptr(), int(cols))
         tail = (*a[17:20], None if span is None else span.data_ptr(), flags)
@@ -357,6 +367,14 @@ class AqlPlan:
         if not self._fin.alive:
             raise RuntimeError("the AQL plan was freed")
         return int(_lib.load().rcbf_aql_plan_dispatches(self._h))  # the handle is live: a count, never an error
+
+    @property
+    def form(self):
+        """The kernel the plan's step packets dispatch: "per_step" (k_safe_step), "fused" (k_safe_steps and its
+        trajectory forms) or "fused_fast" (k_safe_steps_fast, the cars fused plan's straight-line loop)."""
+        if not self._fin.alive:
+            raise RuntimeError("the AQL plan was freed")
+        return FORMS[int(_lib.load().rcbf_aql_plan_form(self._h))]
 
     def times_ns(self):
         """(K, 2) int64 numpy array: each dispatch's start and end (ns, HSA

@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--code-object", default=None,
                     help="the step kernels' code object (default: librcbf_steps.co beside the library); a variant "
                          "build's NAME.co, whose NAME_traj.co is loaded with it")
+    ap.add_argument("--lacks", default="", help="comma list of entry points the library (RCBF_HIP_LIB) does not "
+                                                "have yet: the binding is not asked for them")
     ap.add_argument("--lib-tag", default=None, help="the `lib` field of the output lines (default: new / old)")
     ap.add_argument("--compare-dumps", nargs=2, metavar="DIR", default=None,
                     help="compare two bench.py --dump-outputs directories bit for bit, and exit")
@@ -56,6 +58,8 @@ def main():
     from rcbf_amd import _lib
     if a.old:
         _lib.SIGNATURES.pop("rcbf_aql_safe_step_traj_plan")
+    for name in filter(None, a.lacks.split(",")):
+        _lib.SIGNATURES.pop(name)
     import bench
     from rcbf_amd.aql import AqlQueue
     from rcbf_amd.diff_cbf_qp import CBFQPLayer
@@ -97,6 +101,7 @@ def main():
             env.check_failures()
             print(json.dumps({"lib": a.lib_tag or ("old" if a.old else "new"), "env": a.env, "form": form, "K": K, "B": B,
                               "dispatches": plan.dispatches, "reps": reps,
+                              "kernel": "" if "rcbf_aql_plan_form" not in _lib.SIGNATURES else plan.form,
                               "us_per_step_median": round(ts[len(ts) // 2] / 1e3 / K, 4),
                               "us_per_step_p10": round(ts[len(ts) // 10] / 1e3 / K, 4),
                               "us_per_step_p90": round(ts[9 * len(ts) // 10] / 1e3 / K, 4)}), flush=True)
