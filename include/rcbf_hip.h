@@ -908,6 +908,86 @@ int rcbf_policy_act(const float* packed, int32_t n_o, int32_t n_u, int32_t hidde
                     uint64_t seed, uint64_t counter, int64_t env_offset, hipStream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* SAC target: sampled log-probability, twin-Q forward, TD target          */
+/* ---------------------------------------------------------------------- */
+/* The inference half of the SAC update (rcbf_sac/sac_cbf.py:130-136, under
+ * no_grad), around the safe action (rcbf_obs_safe_action):
+ *   a', log_pi', _ = policy.sample(s')          rcbf_policy_sample
+ *   a'  = get_safe_action(s', a')               rcbf_obs_safe_action
+ *   q1', q2' = critic_target(s', a')            rcbf_critic_q  (or fused below)
+ *   y = r + mask * gamma * (min(q1', q2') - alpha * log_pi')
+ *                                               rcbf_critic_td_target
+ * csrc/rcbf_critic.hip; additions to ABI 13, no existing entry point changes.
+ *
+ * rcbf_policy_sample: GaussianPolicy.sample (model.py:94-106) in one launch.
+ * packed, the shape rules, z / the in-kernel draws, seed, counter and
+ * env_offset are rcbf_policy_act's.  Outputs, fp32 and contiguous:
+ *   u_rl   (B, n_u)            bit for bit what rcbf_policy_act stores with
+ *                              RCBF_POLICY_SAMPLE for the same inputs
+ *   u_mean (B, n_u) [nullable] bit for bit what RCBF_POLICY_MEAN stores
+ *   log_pi (B)      [nullable] sum over c = 0 .. n_u - 1, c ascending, of
+ *       ((-0.5 z_c^2 - log_std_c) - 0.5 log(2 pi)) - log(scale_c (1 - y_c^2) + 1e-6)
+ *     y_c is the fp32 tanhf value the stored action is formed from, log_std
+ *     is clamped to [-20, 2], 0.5 log(2 pi) is the fp32 constant; every
+ *     operation is rounded on its own (no contraction), in this association.
+ *     The reference forms (x_t - mean)^2 / (2 var) with x_t = mean + std z
+ *     (Normal.log_prob): the same quantity as 0.5 z^2, which the kernel
+ *     takes from z directly, without the cancellation of x_t - mean.  Where
+ *     the tanh saturates in fp32 (|x_t| > ~9), 1 - y^2 is 0 and the term is
+ *     -log(1e-6), in the reference as here.
+ * has_log_std = 0 (a module without a log-std head, whose Ws section is
+ * zeros) is refused with RCBF_E_BAD_MODE, as DevicePolicy.act(evaluate=False)
+ * refuses it.  Other errors, B = 0 and capture: as rcbf_policy_act.
+ *
+ * The twin critic (QNetwork, model.py:34-61): two independent MLPs
+ * [n_o + n_u -> H -> H -> 1] on xu = [obs | act] (the kernel concatenates
+ * while it fills LDS).  Shape rules are the policy's.  packed: one device
+ * buffer of rcbf_critic_packed_floats(n_o, n_u, hidden) floats, 16-byte
+ * aligned, net 0 (linear1..3) then net 1 (linear4..6), each with
+ * K1 = n_o + n_u padded to even (<= 18) and the lane l of the policy layout:
+ *   W1p   H K1    [cb < H/32][s < K1/2][l]       = W1[32 cb + (l & 31)][2 s + (l >> 5)]  (0 for k >= n_o + n_u)
+ *   b1    H
+ *   W2p   H H     [cb < H/32][s4 < H/8][l][j<4]  = W2[32 cb + (l & 31)][2 (4 s4 + j) + (l >> 5)]
+ *   b2    H
+ *   w3    H       the output row
+ *   b3    4       (1 used)
+ * in this order: 2 (H (K1 + H + 3) + 4) floats (-1 for a bad shape).
+ * rcbf_amd.critic.DeviceCritic packs a torch module into it.
+ *
+ * rcbf_critic_q: obs (B, n_o), act (B, n_u) -> q1 (B), q2 (B), fp32.  Every
+ * sum is one fp32 fmaf chain, bias first and k ascending, the hidden layers
+ * on the fp32 MFMA and the output unit on the VALU, as rcbf_policy_act
+ * documents: a row's Q-values depend on that row alone, not on B, the tile
+ * shape or the row's place in the batch.  One workgroup per 32 or 64 rows
+ * (rcbf_policy_act's rule); the two nets run one after the other in the same
+ * LDS, (18 + 2 H + 2) x 64 floats at most (133 KiB at H = 256).
+ *
+ * rcbf_critic_td_target: the same forward with the epilogue
+ *   y = reward + (mask * gamma) * (min(q1, q2) - alpha * log_pi)
+ * fp32, no contraction, in exactly this association (Python's, sac_cbf.py:
+ * 135-136); min keeps a NaN like torch.min.  reward, mask, log_pi, y are (B).
+ * alpha_dev [nullable]: a device float the kernel reads instead of the host
+ * value alpha (automatic entropy tuning keeps alpha on the device).  q1, q2
+ * [nullable]: the Q-values as extra outputs.
+ *
+ * Both are stateless and capturable; rows past B are neither read nor
+ * written; B = 0 of a valid shape returns 0 without a launch.  Errors before
+ * any launch: RCBF_E_BAD_SHAPE (a shape above, B < 0, B > 2^31 - 1, packed
+ * not 16-byte or another pointer not 4-byte aligned), RCBF_E_NULL (a required
+ * pointer null). */
+int rcbf_policy_sample(const float* packed, int32_t n_o, int32_t n_u, int32_t hidden, int64_t B,
+                       const float* obs, float* u_rl, float* log_pi, float* u_mean, const float* z,
+                       uint64_t seed, uint64_t counter, int64_t env_offset, int32_t has_log_std,
+                       hipStream_t stream);
+int64_t rcbf_critic_packed_floats(int32_t n_o, int32_t n_u, int32_t hidden);
+int rcbf_critic_q(const float* packed, int32_t n_o, int32_t n_u, int32_t hidden, int64_t B,
+                  const float* obs, const float* act, float* q1, float* q2, hipStream_t stream);
+int rcbf_critic_td_target(const float* packed, int32_t n_o, int32_t n_u, int32_t hidden, int64_t B,
+                          const float* obs, const float* act, const float* reward, const float* mask,
+                          const float* log_pi, float alpha, const float* alpha_dev, float gamma,
+                          float* y, float* q1, float* q2, hipStream_t stream);
+
+/* ---------------------------------------------------------------------- */
 const char* rcbf_version(void);
 int32_t rcbf_abi_version(void);
 /* sizeof(rcbf_params) as compiled, for binding checks (no GPU needed). */

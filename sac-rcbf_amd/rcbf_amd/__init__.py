@@ -13,8 +13,11 @@ safety-layer QP, as hand-written HIP kernels for gfx950 behind a C-ABI
   rcbf_amd.EpisodeStats (episode_stats) <- main.py:98-101,140-144, the loop's episode bookkeeping
   rcbf_amd.DevicePolicy (policy)        <- rcbf_sac/model.py:86-106, the actor's inference forward (one launch)
   rcbf_amd.evaluate_policy (evaluator)  <- main.py:146-177, the evaluation loop on B envs
+  rcbf_amd.DeviceCritic (critic)        <- rcbf_sac/model.py:34-61, the twin critic's inference forward
+  rcbf_amd.sac_cbf.td_target            <- rcbf_sac/sac_cbf.py:130-136, the SAC target (sample, safe action, twin Q)
 """
 from . import _lib  # noqa: F401
+from .critic import DeviceCritic  # noqa: F401
 from .episode_stats import EpisodeStats  # noqa: F401
 from .evaluator import evaluate_policy  # noqa: F401
 from .policy import DevicePolicy  # noqa: F401

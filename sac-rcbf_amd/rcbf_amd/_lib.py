@@ -57,6 +57,7 @@ _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
 _U64 = ctypes.c_uint64
+_F32 = ctypes.c_float
 _PRM = ctypes.POINTER(RcbfParams)
 
 
@@ -154,6 +155,14 @@ SIGNATURES = {
     # the policy forward: packed, n_o, n_u, hidden, B, obs, u_rl, mode, z, seed, counter, env_offset, stream
     "rcbf_policy_act": [_P, _I32, _I32, _I32, _I64, _P, _P, _I32, _P, _U64, _U64, _I64, _P],
     "rcbf_policy_packed_floats": [_I32, _I32, _I32],
+    # the SAC target (rcbf_critic.hip).  sample: packed, n_o, n_u, hidden, B, obs, u_rl, log_pi, u_mean, z, seed,
+    # counter, env_offset, has_log_std, stream
+    "rcbf_policy_sample": [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _P, _U64, _U64, _I64, _I32, _P],
+    "rcbf_critic_packed_floats": [_I32, _I32, _I32],
+    # packed, n_o, n_u, hidden, B, obs, act, q1, q2, stream
+    "rcbf_critic_q": [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _P],
+    # packed, n_o, n_u, hidden, B, obs, act, reward, mask, log_pi, alpha, alpha_dev, gamma, y, q1, q2, stream
+    "rcbf_critic_td_target": [_P, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _P, _F32, _P, _F32, _P, _P, _P, _P],
     "rcbf_aql_run": [_P, _U64],
     "rcbf_aql_plan_times": [_P, _P],
     "rcbf_aql_plan_dispatches": [_P],
@@ -191,6 +200,7 @@ def load():
     lib.rcbf_traj_pack_gp_scratch_bytes.restype = ctypes.c_int64
     lib.rcbf_traj_episode_stats_scratch_bytes.restype = ctypes.c_int64
     lib.rcbf_policy_packed_floats.restype = ctypes.c_int64
+    lib.rcbf_critic_packed_floats.restype = ctypes.c_int64
     if lib.rcbf_abi_version() != ABI_VERSION or lib.rcbf_params_size() != ctypes.sizeof(RcbfParams):
         raise RuntimeError("librcbf_hip.so ABI mismatch (rebuild with `python __graft_entry__.py build`)")
     _bind_fast(lib)

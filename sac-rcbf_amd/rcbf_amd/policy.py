@@ -11,8 +11,10 @@ once into the layout rcbf_policy_act reads (include/rcbf_hip.h) and computes
 
 in one kernel (csrc/rcbf_policy.hip), fp32, every sum one fmaf chain in a fixed
 order: row i of a batched call is bit for bit the action a single-env call on
-that row computes.  Inference only -- no log_prob, no autograd; training keeps
-the torch module, and refresh() re-packs it after an optimiser step.
+that row computes.  sample() adds GaussianPolicy.sample's log-probability and
+mean action (csrc/rcbf_critic.hip), what the SAC target needs.  Inference only
+-- no autograd; training keeps the torch module, and refresh() re-packs it
+after an optimiser step.
 """
 import torch
 
@@ -162,3 +164,48 @@ class DevicePolicy:
                                      _lib.stream_of(self.device))
         _lib.check(rc, "rcbf_policy_act")
         return out
+
+    def sample(self, obs, z=None, seed=None, counter=None, out=None):
+        """GaussianPolicy.sample (model.py:94-106): obs (B, n_o) ->
+        (action (B, n_u), log_pi (B, 1), mean_action (B, n_u)), in one launch
+        (rcbf_policy_sample).  The action is bit for bit act(evaluate=False)'s
+        for the same z or (seed, counter) -- the default counter is act's, one
+        per call -- and the mean action act(evaluate=True)'s; log_pi is the
+        sample's log-probability with the tanh correction (the formula and its
+        rounding order: include/rcbf_hip.h).  `out`: a triple of tensors to
+        write into.  One library call; nothing is read from the device."""
+        self._check(obs, "obs", self.n_o)
+        B = int(obs.shape[0])
+        if self._log_std_head is None:
+            raise NotImplementedError("sample needs a log-std head: the reference's DeterministicPolicy.sample "
+                                      "shares one noise vector across rows, which is not reproduced")
+        if out is None:
+            out = (torch.empty(B, self.n_u, dtype=torch.float32, device=self.device),
+                   torch.empty(B, 1, dtype=torch.float32, device=self.device),
+                   torch.empty(B, self.n_u, dtype=torch.float32, device=self.device))
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out must be (action, log_pi, mean_action)")
+            for t, name, width in zip(out, ("out[0]", "out[1]", "out[2]"), (self.n_u, 1, self.n_u)):
+                self._check(t, name, width)
+                if t.shape[0] != B:
+                    raise ValueError(f"{name} has {t.shape[0]} rows, obs {B}")
+        if z is not None:
+            self._check(z, "z", self.n_u)
+            if z.shape[0] != B:
+                raise ValueError(f"z has {z.shape[0]} rows, obs {B}")
+        if self.device.type != "cuda":
+            raise ValueError("DevicePolicy.sample needs HIP device tensors")
+        if counter is None and z is None:
+            counter = self._counter
+            self._counter += 1
+        action, log_pi, mean_action = out
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            rc = lib.rcbf_policy_sample(_lib.ptr(self.packed), self.n_o, self.n_u, self.hidden, B, _lib.ptr(obs),
+                                        _lib.ptr(action), _lib.ptr(log_pi), _lib.ptr(mean_action), _lib.ptr(z),
+                                        (self.seed if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF,
+                                        int(counter or 0) & 0xFFFFFFFFFFFFFFFF, self.env_offset, 1,
+                                        _lib.stream_of(self.device))
+        _lib.check(rc, "rcbf_policy_sample")
+        return action, log_pi, mean_action

@@ -68,6 +68,36 @@ def get_safe_action(cbf_layer, obs_batch, action_batch, dynamics_model):
     return out.squeeze(0) if expand else out
 
 
+def td_target(policy, critic_target, cbf_layer, dynamics_model, next_obs, reward, mask, alpha, gamma, diff_qp=True,
+              z=None, counter=None):
+    """The no_grad block of RCBF_SAC.update_parameters (sac_cbf.py:130-136):
+
+        a', log_pi', _ = policy.sample(s')
+        a' = get_safe_action(s', a')                      if diff_qp
+        y  = r + mask * gamma * (min(critic_target(s', a')) - alpha * log_pi')
+
+    policy is a DevicePolicy, critic_target a DeviceCritic (refresh() it after
+    soft_update).  Three library calls with the prior disturbance --
+    DevicePolicy.sample, the safe action's one launch, DeviceCritic.td_target
+    -- and the safe action's two more with a fitted GP.  next_obs, reward and
+    mask may be what ReplayMemory.sample_tensors hands out (strided fp64
+    views); alpha is a float or a one-element device tensor; z (B, n_u) are the
+    draws, else the policy's in-kernel ones at `counter`.  Returns y (B, 1)
+    fp32.  A failed QP raises like get_safe_action."""
+    dev = policy.device
+    obs = _f32(next_obs, dev)
+    B = obs.shape[0] if obs.dim() == 2 else -1
+    reward, mask = (_f32(t, dev).reshape(-1, 1) for t in (reward, mask))
+    if obs.dim() != 2 or reward.shape[0] != B or mask.shape[0] != B:
+        raise ValueError(f"expected next_obs (B, n_o), reward (B,) or (B, 1) and mask alike, got "
+                         f"{tuple(obs.shape)} / {tuple(reward.shape)} / {tuple(mask.shape)}")
+    with torch.no_grad():
+        action, log_pi, _ = policy.sample(obs, z=z, counter=counter)
+        if diff_qp:
+            action = get_safe_action(cbf_layer, obs, action, dynamics_model)
+        return critic_target.td_target(obs, action, reward, mask, log_pi, alpha, gamma)
+
+
 class _HostSlot:
     """A pinned host block per device and thread for rcbf_gp_obs_safe_action: the action
     (<= 2 floats) at byte 0, the QP status at byte 32, the completion word at
